@@ -10,6 +10,9 @@ N = 1 (default) -- BASELINE config 2: nreduce = 64 Mi doubles, 1 MI355X,
   2-PE active set (K = 2 inputs: the PE's own source and its peer's, both in
   HBM) through the C ABI (osgpu_combine).  Algorithmic bytes per step
   B = (K + 1) * nreduce * 8 (2 reads + 1 write), value = steps * B / t.
+  A plain run sets up (seeded inputs), warms up, times the --steps launches,
+  writes the target with --dump-outputs DIR and prints the line.  Everything
+  below is measured only with --full, after the timed steps.
   Extra fields: roofline (HIP events on the launch stream + PMC traffic from
   profiles/), the full C-API call (2 PEs, timed in C), the host-staged
   (PCIe-inclusive) rate, the data-movement collectives (copy kernel roofline,
@@ -25,7 +28,9 @@ N > 1 (torchrun, one process per GPU) -- one PE per GPU, every PE calls
   intra-node shared-memory runtime (tests/support/pe_shm.c); a sampled
   bit-exact parity check against the oracle is reported.  value = steps *
   (N + 1) * nreduce * 8 / t (SURVEY.md 8d aggregate: sum over GPUs of the
-  shard-fold bytes), t = the max over ranks.  Then, in the same run: RCCL
+  shard-fold bytes), t = the max over ranks; --dump-outputs DIR writes every
+  PE's target.  With --full (else the run ends there): the parity check, the
+  link probe, the push exchange, and then, in the same run: RCCL
   allreduce on the same buffers (forced: FP sum within tolerance), BASELINE
   config 4 (nreduce = 1 Gi: the exact team kernel over the heaps, and RCCL
   beside it) and config 5 (float min/max/prod,
@@ -251,15 +256,51 @@ def default_detail(n_gpus):
     return os.path.join(ROOT, "gpurun_out", f"bench_detail_n{n_gpus}.json")
 
 
+DUMP_MAX_BYTES = 32 << 20   # --dump-outputs: all files of one run together stay under this
+DUMP_SEED = 0x0D0F          # ... and the sample of a larger array is drawn with this seed
+
+
+def dump_outputs(dirname, arrays, torch, budget=DUMP_MAX_BYTES):
+    """--dump-outputs: every (name, tensor) of `arrays` -- what the last timed
+    step left in the arrays its caller receives -- as DIR/<name>.npy, float64.
+    An array that fits its share of `budget` is written whole; of a larger
+    one, the elements at a fixed sample of indices (drawn on the CPU from
+    DUMP_SEED and the array's length alone, ascending), so two runs with the
+    same arguments write the same elements.  Returns what was written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = (budget // max(len(arrays), 1) - 4096) // 8   # elements per file, header aside
+    done = {}
+    for name, x in arrays:
+        n = x.numel()
+        if n > share:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, n, (share,), generator=g).sort().values
+            x = x[idx.to(x.device)]
+        v = x.detach().cpu().numpy().astype(np.float64, copy=False)
+        np.save(os.path.join(dirname, name + ".npy"), v)
+        done[name] = {"elements": int(v.size), "of": int(n), "dtype": "float64",
+                      "sampled": bool(v.size < n)}
+    return done
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--nreduce", type=int, default=64 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and check "
+                         "(rooflines, PMC traffic, team kernels, C-API call, host staging, "
+                         "collectives, CPU baselines; N>1: parity, link probe, RCCL, configs "
+                         "4 and 5); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of at most DUMP_MAX_BYTES when larger)")
     ap.add_argument("--no-rccl", action="store_true", help="N>1: skip the RCCL runs")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the side measurements (N=1: north star / config 3 "
+                    help="with --full: skip the side measurements (N=1: north star / config 3 "
                          "kernel rates; N>1: config 4, config 5, collectives, probes)")
     ap.add_argument("--c4-nreduce", type=int, default=1 << 30)
     ap.add_argument("--c5-nreduce", type=int, default=128 << 20)
@@ -1168,8 +1209,10 @@ def bench_single(args):
     L = osgpu.load()
     n = args.nreduce
     dev = torch.device("cuda:0")
-    a = torch.empty(n, dtype=torch.float64, device=dev).uniform_(1.0, 2.0)
-    b = torch.empty(n, dtype=torch.float64, device=dev).uniform_(1.0, 2.0)
+    # seeded: the same arguments give the same inputs in every run and build
+    g = torch.Generator(device=dev).manual_seed(2 * 64 + 1)
+    a = torch.empty(n, dtype=torch.float64, device=dev).uniform_(1.0, 2.0, generator=g)
+    b = torch.empty(n, dtype=torch.float64, device=dev).uniform_(1.0, 2.0, generator=g)
     out = torch.empty(n, dtype=torch.float64, device=dev)
     stream = torch.cuda.Stream(device=dev)
     srcs = (ctypes.c_void_p * 2)(a.data_ptr(), b.data_ptr())
@@ -1202,18 +1245,22 @@ def bench_single(args):
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
     kavg = e_beg.elapsed_time(e_end) * 1e-3 / args.steps
-    # after the timed region: the per-launch spread (an event pair per launch)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(args.steps)]
-    for e0, e1 in ev:
-        e0.record(stream)
-        step()
-        e1.record(stream)
-    torch.cuda.synchronize()
-    kms = sorted(s.elapsed_time(e) for s, e in ev)
-    # and once the clocks have settled (launches 1-100 of a process run
-    # 1-3 % slower, tools/warm_probe.py): 100 more, one event pair
-    ksteady = span_per_launch(torch, stream, step, 100)
+    # the target as the last timed step left it, before anything launches again
+    dumped = (dump_outputs(args.dump_outputs, [("target", out)], torch)
+              if args.dump_outputs else None)
+    if args.full:
+        # after the timed region: the per-launch spread (an event pair per launch)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(args.steps)]
+        for e0, e1 in ev:
+            e0.record(stream)
+            step()
+            e1.record(stream)
+        torch.cuda.synchronize()
+        kms = sorted(s.elapsed_time(e) for s, e in ev)
+        # and once the clocks have settled (launches 1-100 of a process run
+        # 1-3 % slower, tools/warm_probe.py): 100 more, one event pair
+        ksteady = span_per_launch(torch, stream, step, 100)
     B = 3 * n * 8
     res = {
         "metric": METRIC,
@@ -1233,6 +1280,23 @@ def bench_single(args):
                                "device-resident combine kernel",
                    "nreduce": n, "K": 2, "bytes_per_step": B},
     }
+    if dumped is not None:
+        res["outputs"] = dumped
+    if not args.full:
+        # the plain run ends here: the line's roofline is the timed steps' own
+        # event span, its traffic the newest PMC file of profiles/
+        tr = load_traffic(n=n)
+        res["roofline"] = {
+            "bound": "hbm", "achieved": B / kavg / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": B / kavg / 1e9 / HBM_PEAK_GBS,
+            "traffic": tr.get("bytes_per_launch") if tr else None,
+            "traffic_source": tr.get("source") if tr else None,
+            "kernel": COMBINE_LABEL, "kernel_avg_us": kavg * 1e6,
+            "kernel_avg_how": "HIP event span over the K timed launches on the launch stream / K",
+            "algorithmic_bytes_per_launch": B}
+        res["side_measurements"] = "not run (--full runs them)"
+        print(fit_line(res, args.detail or default_detail(1)), flush=True)
+        return
     del a, b, out
     torch.cuda.empty_cache()
     # this box's streaming ceiling at the same footprint (copy kernel: 1 read
@@ -1755,7 +1819,8 @@ def bench_multi(args):
     seg_bytes = (n * 8 + (2 << 20) - 1) // (2 << 20) * (2 << 20)
     n4 = args.c4_nreduce
     c4_bytes = (n4 * 8 + (2 << 20) - 1) // (2 << 20) * (2 << 20)
-    with_c4 = not args.no_extra
+    extra = args.full and not args.no_extra   # the side measurements run
+    with_c4 = extra
     heap_bytes = 2 * seg_bytes + (2 * c4_bytes if with_c4 else 0)
     state["phase"] = "heap"
     mapped = []
@@ -1893,8 +1958,15 @@ def bench_multi(args):
         if ndev < world:  # a rehearsal with ranks sharing GPUs: no xGMI involved
             res["roofline"]["frac"] = None
             res["roofline"]["note"] += "; ranks share a GPU here, so no link is used"
-        res["parity_sample"] = _sample_parity(rank, world, src, tgt, n, "sum", dist)
+        if args.dump_outputs:   # every PE's own target, as the last timed step left it
+            res["outputs"] = dump_outputs(args.dump_outputs, [(f"target_pe{rank}", tgt)], torch,
+                                          DUMP_MAX_BYTES // world)
+        if args.full:
+            res["parity_sample"] = _sample_parity(rank, world, src, tgt, n, "sum", dist)
         _log(rank, "team done")
+    else:
+        res["team_error"] = "HIP IPC export/import of the device heaps failed on some rank"
+    if team_ok and args.full:
         # ---- the link itself, measured right away (the roofline's peak):
         # every GPU at once copies one chunk per peer with the copy kernel,
         # remote reads and remote writes
@@ -1953,8 +2025,6 @@ def bench_multi(args):
             res["team_push"] = {"error": repr(e)[:300]}
         finally:
             L.osgpu_set_team_exchange(-1)
-    else:
-        res["team_error"] = "HIP IPC export/import of the device heaps failed on some rank"
 
     # ---- the team kernel's two launch shapes over the same heaps (ADVICE
     # r05): every rank launches its shard of the double sum with the local
@@ -1962,7 +2032,7 @@ def bench_multi(args):
     # with the remote ones (register form at 2, rounds of 2) that the TEAM
     # path picks when members sit on other GPUs -- kernel only, all ranks at
     # once, max over ranks; bit-identical outputs checked
-    if team_ok and not args.no_extra:
+    if team_ok and extra:
         state["phase"] = "team_shapes"
         try:
             res["team_shapes_ab"] = _team_shapes_ab(L, osgpu, torch, dist, rank, world, bases,
@@ -1976,7 +2046,7 @@ def bench_multi(args):
     # to_all and earns no scaling credit: it only shows that the per-GPU HBM
     # fold runs at the N = 1 rate while every GPU is busy.  `value` above is
     # the whole to_all, whose exchange is xGMI-bound.
-    if not args.no_extra:
+    if extra:
         state["phase"] = "local_fold"
         try:
             other = htgt[: n * 8].view(torch.float64)
@@ -2005,7 +2075,8 @@ def bench_multi(args):
 
     # ---- RCCL on the same buffers, then BASELINE config 4 (1 Gi per PE)
     rccl_ok = False
-    if not args.no_rccl:
+    # (a side measurement, unless the team path is unusable and RCCL carries the line)
+    if (args.full or res["value"] is None) and not args.no_rccl:
         state["phase"] = "rccl"
         try:
             uid = (ctypes.c_char * 128)()
@@ -2044,7 +2115,7 @@ def bench_multi(args):
                 res["rccl"]["note"] = ("ranks share a GPU in this run: RCCL refuses more than "
                                        "one rank per GPU, so no RCCL leg can run here")
         # the automatic path's integer dispatch to RCCL, bit-exact vs the oracle
-        if rccl_ok:
+        if rccl_ok and args.full:
             state["phase"] = "rccl_integer"
             try:
                 res["rccl_integer_auto"] = _rccl_integer_legs(
@@ -2099,7 +2170,7 @@ def bench_multi(args):
 
     # ---- BASELINE config 5: float min/max/prod, 128 Mi per PE, sources and
     # targets in pinned HOST memory: H2D + on-GPU exchange + D2H (STAGED path)
-    if not args.no_extra:
+    if extra:
         state["phase"] = "config5"
         try:
             L.osgpu_set_path(osgpu.PATH_AUTO)
@@ -2154,7 +2225,7 @@ def bench_multi(args):
 
     # ---- fcollect64 on the same machinery, one PE per
     # GPU -- device heaps over xGMI (COPY path), RCCL allgather, host staging
-    if not args.no_extra:
+    if extra:
         state["phase"] = "collectives"
         try:
             res["collectives"] = _multi_fcollect(L, osgpu, torch, dist, rank, world, dev, hsrc,
@@ -2166,7 +2237,7 @@ def bench_multi(args):
 
     # ---- BASELINE config 1's shape across GPUs: fused one-launch path vs
     # host barriers (DESIGN_HISTORY.md 10)
-    if team_ok and not args.no_extra:
+    if team_ok and extra:
         state["phase"] = "small_calls"
         try:
             res["small_calls"] = _multi_small(L, osgpu, torch, dist, rank, world, hsrc, htgt, PES,

@@ -117,6 +117,50 @@ def test_defaults_single_gpu_within_minutes():
     assert a.gpus == 1 and a.nreduce == 64 << 20 and 0 < a.steps <= 100 and 0 <= a.warmup
 
 
+def _parse(*argv):
+    sys.path.insert(0, ROOT)
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", *argv]
+        return bench.parse()
+    finally:
+        sys.argv = old
+
+
+def test_plain_run_is_the_default():
+    """--full and --dump-outputs are off unless asked for."""
+    a = _parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = _parse("--full", "--dump-outputs", "somewhere")
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """A small array is written whole, a large one as the same seeded sample
+    in every run, float64, all files together within DUMP_MAX_BYTES."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_MAX_BYTES <= 64 * 10**6
+    small = torch.arange(1000, dtype=torch.float64) * 0.5
+    big = torch.arange(3 << 20, dtype=torch.float32)
+    budget = 4 << 20
+    for d in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / d), [("small", small), ("big", big)], torch,
+                                  budget)
+        assert not info["small"]["sampled"] and info["big"]["sampled"]
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float64 and a_big.dtype == np.float64
+    assert np.array_equal(a_small, small.numpy())
+    # the sample: ascending positions of `big` (whose values are its indices)
+    assert a_big.size < big.numel() and np.all(np.diff(a_big) >= 0)
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= budget
+
+
 def test_bench_names_the_shipped_lds_tile():
     """bench.py looks the LDS team kernel up by its rocprof name, whose last
     template argument is team.hip's OSGPU_TEAM_LDS_U: the two must agree."""

@@ -8,7 +8,7 @@ average.  Not part of the product.
 
 PROF_DIR holds run_kernel_trace.csv / run_kernel_stats.csv from
 `rocprofv3 --kernel-trace --stats -d PROF_DIR -o run --output-format csv --
-python3 bench.py --gpus 1 --steps K --warmup W` (tools/gpu_round.sh step
+python3 bench.py --full --gpus 1 --steps K --warmup W` (tools/gpu_round.sh step
 `proffull`).  Bursts: launches of the headline kernel at the full grid less
 than 1 ms apart; the timed region is the first burst of at least K launches (the W warm-up
 launches form a shorter burst before it)."""
@@ -52,7 +52,7 @@ def main(prof, bench_log, out_path):
             {"calls": int(r["Calls"]), "avg_us": float(r["AverageNs"]) / 1e3}
             for r in stats if "team_" in r["Name"]}
     out = {"kernel": "combine_lds_kernel<double, 0, 2, 2>", "grid": grid,
-           "command": f"rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 "
+           "command": f"rocprofv3 --kernel-trace --stats -- python3 bench.py --full --gpus 1 "
                       f"--steps {steps} --warmup {warmup}",
            "timed_region_launches": len(timed),
            "avg_duration_us_timed": statistics.mean(dur),
