@@ -24,20 +24,11 @@
 #include <stdint.h>
 #include <stddef.h>
 
-#include "elem_ops.hpp"
-#include "combine.hpp"
+#include "kernel_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace osgpu {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-union Vec16 {
-    u32x4 v;
-    T e[16 / sizeof(T)];
-};
 
 template <typename T, int K>
 struct Inputs {
@@ -108,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void combine_vec_kernel(
 
     // edges: head elements [0, head) and tail [tail_start, tail_start + ...)
     if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
-        size_t e = threadIdx.x < head ? threadIdx.x : tail_start + (threadIdx.x - head);
+        const size_t e = edge_index(head, tail_start);
         out[e] = fold_scalar<T, OP, K>(in, e);
     }
 
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(64 * K) void combine_lds_kernel(T *out, Inputs<T, K
     constexpr int V = 64 * U;  // vectors per input per tile
     __shared__ u32x4 tile[K][V];
     if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
-        size_t e = threadIdx.x < head ? threadIdx.x : tail_start + (threadIdx.x - head);
+        const size_t e = edge_index(head, tail_start);
         out[e] = fold_scalar<T, OP, K>(in, e);
     }
     const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
@@ -240,13 +231,9 @@ template <typename T, int OP, int K>
 static hipError_t launch_k(T *out, const T *const *srcs, size_t n, hipStream_t s)
 {
     Inputs<T, K> in;
-    uintptr_t phase = (uintptr_t) out & 15;
-    bool same_phase = (phase % sizeof(T)) == 0;
-    for (int k = 0; k < K; k++) {
-        in.p[k] = srcs[k];
-        if (((uintptr_t) srcs[k] & 15) != phase) same_phase = false;
-    }
-    if (!same_phase || sizeof(T) > 16) {
+    for (int k = 0; k < K; k++) in.p[k] = srcs[k];
+    const VecSplit vs = vec_split(sizeof(T), n, &out, 1, srcs, K);
+    if (!vs.vec) {
         size_t blocks = (n + kBlock - 1) / kBlock;
         if (blocks > 8192) blocks = 8192;
         if (blocks == 0) blocks = 1;
@@ -256,36 +243,23 @@ static hipError_t launch_k(T *out, const T *const *srcs, size_t n, hipStream_t s
     }
     constexpr int W = 16 / sizeof(T);
     constexpr int U = Unroll<K>::value;
-    size_t head = phase ? (16 - phase) / sizeof(T) : 0;
-    if (head > n) head = n;
-    size_t nvec = (n - head) / W;
-    size_t tail_start = head + nvec * W;
-    int nedge = (int) (head + (n - tail_start));
-    // tiles of V vectors, one per workgroup of `threads`; at most
-    // max_launch_threads() per launch (combine.hpp): the first launch takes the
-    // edges, the others the next runs of tiles through shifted pointers
+    // tiles of V vectors, one per workgroup of `threads`: the first launch
+    // takes the edges, the others the next runs of tiles through shifted
+    // pointers (for_each_tile_run)
     auto launch = [&](size_t V, unsigned threads, auto kernel) -> hipError_t {
-        size_t tiles = (nvec + V - 1) / V;
-        if (tiles == 0) tiles = 1;
-        const size_t lim = max_launch_threads() / threads;
-        const size_t per_launch = lim ? lim : 1;
-        for (size_t t0 = 0; t0 < tiles; t0 += per_launch) {
-            const size_t nt = tiles - t0 < per_launch ? tiles - t0 : per_launch;
-            const size_t nv = nvec - t0 * V < nt * V ? nvec - t0 * V : nt * V;
+        return for_each_tile_run(vs.nvec, V, threads, 1, [&](size_t t0, size_t nt, size_t nv) {
             if (t0 == 0) {
                 hipLaunchKernelGGL(kernel, dim3((unsigned) nt), dim3(threads), 0, s, out, in, nv,
-                                   head, tail_start, nedge);
+                                   vs.head, vs.tail_start, vs.nedge);
             } else {
-                const size_t off = head + t0 * V * W;
+                const size_t off = vs.head + t0 * V * W;
                 Inputs<T, K> ic;
                 for (int k = 0; k < K; k++) ic.p[k] = in.p[k] + off;
                 hipLaunchKernelGGL(kernel, dim3((unsigned) nt), dim3(threads), 0, s, out + off, ic, nv,
                                    (size_t) 0, (size_t) 0, 0);
             }
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            return hipGetLastError();
+        });
     };
     if constexpr (K >= 2 && K <= kCombineLdsMaxK) {
         constexpr int UL = K == 2 ? OSGPU_COMBINE_LDS_U2 : kCombineLdsU;
@@ -325,63 +299,15 @@ static hipError_t launch_op(void *out_, const void *const *srcs_, int k, size_t 
     return err;
 }
 
-template <typename T>
-static hipError_t launch_int(int op, void *out, const void *const *srcs, int k, size_t n,
-                             hipStream_t s)
-{
-    switch (op) {
-    case OP_SUM: return launch_op<T, OP_SUM>(out, srcs, k, n, s);
-    case OP_PROD: return launch_op<T, OP_PROD>(out, srcs, k, n, s);
-    case OP_AND: return launch_op<T, OP_AND>(out, srcs, k, n, s);
-    case OP_OR: return launch_op<T, OP_OR>(out, srcs, k, n, s);
-    case OP_XOR: return launch_op<T, OP_XOR>(out, srcs, k, n, s);
-    case OP_MAX: return launch_op<T, OP_MAX>(out, srcs, k, n, s);
-    case OP_MIN: return launch_op<T, OP_MIN>(out, srcs, k, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t launch_real(int op, void *out, const void *const *srcs, int k, size_t n,
-                              hipStream_t s)
-{
-    switch (op) {
-    case OP_SUM: return launch_op<T, OP_SUM>(out, srcs, k, n, s);
-    case OP_PROD: return launch_op<T, OP_PROD>(out, srcs, k, n, s);
-    case OP_MAX: return launch_op<T, OP_MAX>(out, srcs, k, n, s);
-    case OP_MIN: return launch_op<T, OP_MIN>(out, srcs, k, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t launch_cplx(int op, void *out, const void *const *srcs, int k, size_t n,
-                              hipStream_t s)
-{
-    switch (op) {
-    case OP_SUM: return launch_op<T, OP_SUM>(out, srcs, k, n, s);
-    case OP_PROD: return launch_op<T, OP_PROD>(out, srcs, k, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_combine(int type, int op, void *out, const void *const *srcs, int k,
                           size_t n, hipStream_t s)
 {
     if (k < 1 || out == nullptr) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    switch (type) {
-    case T_SHORT: return launch_int<int16_t>(op, out, srcs, k, n, s);
-    case T_INT: return launch_int<int32_t>(op, out, srcs, k, n, s);
-    case T_LONG:
-    case T_LONGLONG: return launch_int<int64_t>(op, out, srcs, k, n, s);
-    case T_FLOAT: return launch_real<float>(op, out, srcs, k, n, s);
-    case T_DOUBLE: return launch_real<double>(op, out, srcs, k, n, s);
-    case T_COMPLEXF: return launch_cplx<cfloat>(op, out, srcs, k, n, s);
-    case T_COMPLEXD: return launch_cplx<cdouble>(op, out, srcs, k, n, s);
-    case T_LONGDOUBLE: return launch_longdouble(op, out, srcs, k, n, s);
-    }
-    return hipErrorInvalidValue;
+    if (type == T_LONGDOUBLE) return launch_longdouble(op, out, srcs, k, n, s);
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return launch_op<typename decltype(t)::type, decltype(o)::value>(out, srcs, k, n, s);
+    });
 }
 
 }  // namespace osgpu

@@ -30,12 +30,11 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "combine.hpp"
+#include "kernel_common.hpp"
 
 namespace osgpu {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));  // dword-aligned 16-B load
 
 constexpr int kThreads = 256;

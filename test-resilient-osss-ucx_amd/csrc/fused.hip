@@ -62,24 +62,15 @@
 
 #include <type_traits>
 
-#include "combine.hpp"
-#include "elem_ops.hpp"
+#include "kernel_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace osgpu {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int kFBlock = 256;
-
-template <typename T>
-union FVec {
-    u32x4 v;
-    T e[16 / sizeof(T)];
-};
 
 __device__ __forceinline__ unsigned long long ld_sys(const unsigned long long *p)
 {
@@ -444,14 +435,14 @@ __global__ __launch_bounds__(kFBlock) void fused_kernel(FusedArgs a)
             }
             const size_t stride = (size_t) gridDim.x * kFBlock;
             for (size_t j = (size_t) blockIdx.x * kFBlock + threadIdx.x; j < a.nvec; j += stride) {
-                FVec<T> in[kMaxTeam];
+                Vec16<T> in[kMaxTeam];
 #pragma unroll
                 for (int p = 0; p < kMaxTeam; p++)
                     if (p < a.P)
                         in[p].v = __builtin_nontemporal_load(
                             reinterpret_cast<const u32x4 *>(static_cast<const T *>(a.src[p]) +
                                                             a.head) + j);
-                FVec<T> out[kMaxTeam];
+                Vec16<T> out[kMaxTeam];
 #pragma unroll
                 for (int w = 0; w < W; w++) {
                     T x[kMaxTeam], r[kMaxTeam];
@@ -531,25 +522,13 @@ __global__ __launch_bounds__(kFBlock) void fused_kernel(FusedArgs a)
 template <typename T, int OP>
 hipError_t fused_launch_t(FusedArgs a, hipStream_t s)
 {
-    constexpr int W = 16 / sizeof(T);
-    const uintptr_t phase = (uintptr_t) a.src[0] & 15;
-    bool vec = (phase % sizeof(T)) == 0;
-    for (int p = 0; p < a.P; p++) vec = vec && (((uintptr_t) a.src[p] & 15) == phase);
-    for (int d = 0; d < a.D; d++) vec = vec && (((uintptr_t) a.dst[d] & 15) == phase);
-    size_t work;
-    if (vec) {
-        size_t head = phase ? (16 - phase) / sizeof(T) : 0;
-        if (head > a.n) head = a.n;
-        a.head = head;
-        a.nvec = (a.n - head) / W;
-        a.tail_start = head + a.nvec * W;
-        a.nedge = (int) (head + (a.n - a.tail_start));
-        work = a.nvec;
-    } else {
-        a.head = a.nvec = a.tail_start = 0;
-        a.nedge = 0;
-        work = a.n;
-    }
+    const VecSplit vs = vec_split(sizeof(T), a.n, a.src, a.P, a.dst, a.D);
+    const bool vec = vs.vec;
+    a.head = vs.head;
+    a.nvec = vs.nvec;
+    a.tail_start = vs.tail_start;
+    a.nedge = vs.nedge;
+    const size_t work = vec ? a.nvec : a.n;
     size_t blocks = (work + kFBlock - 1) / kFBlock;
     if (blocks < 1) blocks = 1;
     if (blocks > (size_t) a.max_blocks) blocks = (size_t) a.max_blocks;
@@ -560,37 +539,6 @@ hipError_t fused_launch_t(FusedArgs a, hipStream_t s)
         hipLaunchKernelGGL((fused_kernel<T, OP, false>), dim3((unsigned) blocks), dim3(kFBlock),
                            0, s, a);
     return hipGetLastError();
-}
-
-#define FUSED_CASE(OPC)                                                        \
-    case OPC: return fused_launch_t<T, OPC>(a, s);
-
-template <typename T>
-hipError_t fused_int(int op, const FusedArgs &a, hipStream_t s)
-{
-    switch (op) {
-        FUSED_CASE(OP_SUM) FUSED_CASE(OP_PROD) FUSED_CASE(OP_AND) FUSED_CASE(OP_OR)
-        FUSED_CASE(OP_XOR) FUSED_CASE(OP_MAX) FUSED_CASE(OP_MIN)
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-hipError_t fused_real(int op, const FusedArgs &a, hipStream_t s)
-{
-    switch (op) {
-        FUSED_CASE(OP_SUM) FUSED_CASE(OP_PROD) FUSED_CASE(OP_MAX) FUSED_CASE(OP_MIN)
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-hipError_t fused_cplx(int op, const FusedArgs &a, hipStream_t s)
-{
-    switch (op) {
-        FUSED_CASE(OP_SUM) FUSED_CASE(OP_PROD)
-    }
-    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -632,17 +580,9 @@ hipError_t launch_fused(int type, int op, const FusedArgs &a, hipStream_t s)
     if (a.P < 2 || a.P > kMaxTeam || a.D < 1 || a.D > kMaxTeam || a.me < 0 || a.me >= a.P ||
         a.max_blocks < 1 || a.max_blocks > kFusedBlocksPerGpu)
         return hipErrorInvalidValue;
-    switch (type) {
-    case T_SHORT: return fused_int<int16_t>(op, a, s);
-    case T_INT: return fused_int<int32_t>(op, a, s);
-    case T_LONG:
-    case T_LONGLONG: return fused_int<int64_t>(op, a, s);
-    case T_FLOAT: return fused_real<float>(op, a, s);
-    case T_DOUBLE: return fused_real<double>(op, a, s);
-    case T_COMPLEXF: return fused_cplx<cfloat>(op, a, s);
-    case T_COMPLEXD: return fused_cplx<cdouble>(op, a, s);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return fused_launch_t<typename decltype(t)::type, decltype(o)::value>(a, s);
+    });
 }
 
 }  // namespace osgpu

@@ -23,8 +23,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "combine.hpp"
-#include "elem_ops.hpp"
+#include "kernel_common.hpp"
 #include "x87.hpp"
 
 #pragma clang fp contract(off)
@@ -62,68 +61,14 @@ void fold_ld(void *acc_v, const void *in_v, size_t n)
 
 typedef void (*FoldFn)(void *, const void *, size_t);
 
-template <typename T>
-FoldFn int_fn(int op)
-{
-    switch (op) {
-    case OP_SUM: return fold_n<T, OP_SUM>;
-    case OP_PROD: return fold_n<T, OP_PROD>;
-    case OP_AND: return fold_n<T, OP_AND>;
-    case OP_OR: return fold_n<T, OP_OR>;
-    case OP_XOR: return fold_n<T, OP_XOR>;
-    case OP_MAX: return fold_n<T, OP_MAX>;
-    case OP_MIN: return fold_n<T, OP_MIN>;
-    }
-    return nullptr;
-}
-
-template <typename T>
-FoldFn real_fn(int op)
-{
-    switch (op) {
-    case OP_SUM: return fold_n<T, OP_SUM>;
-    case OP_PROD: return fold_n<T, OP_PROD>;
-    case OP_MAX: return fold_n<T, OP_MAX>;
-    case OP_MIN: return fold_n<T, OP_MIN>;
-    }
-    return nullptr;
-}
-
-template <typename T>
-FoldFn cplx_fn(int op)
-{
-    switch (op) {
-    case OP_SUM: return fold_n<T, OP_SUM>;
-    case OP_PROD: return fold_n<T, OP_PROD>;
-    }
-    return nullptr;
-}
-
-FoldFn ld_fn(int op)
-{
-    switch (op) {
-    case OP_SUM: return fold_ld<OP_SUM>;
-    case OP_PROD: return fold_ld<OP_PROD>;
-    case OP_MAX: return fold_ld<OP_MAX>;
-    case OP_MIN: return fold_ld<OP_MIN>;
-    }
-    return nullptr;
-}
-
 FoldFn fold_fn(int type, int op)
 {
-    switch (type) {
-    case T_SHORT: return int_fn<int16_t>(op);
-    case T_INT: return int_fn<int32_t>(op);
-    case T_LONG:
-    case T_LONGLONG: return int_fn<int64_t>(op);
-    case T_FLOAT: return real_fn<float>(op);
-    case T_DOUBLE: return real_fn<double>(op);
-    case T_COMPLEXF: return cplx_fn<cfloat>(op);
-    case T_COMPLEXD: return cplx_fn<cdouble>(op);
-    case T_LONGDOUBLE: return ld_fn(op);
-    }
-    return nullptr;
+    if (type == T_LONGDOUBLE)
+        return dispatch_ld_op(op, (FoldFn) nullptr,
+                              [](auto o) -> FoldFn { return fold_ld<decltype(o)::value>; });
+    return dispatch_type_op(type, op, (FoldFn) nullptr, [](auto t, auto o) -> FoldFn {
+        return fold_n<typename decltype(t)::type, decltype(o)::value>;
+    });
 }
 
 }  // namespace

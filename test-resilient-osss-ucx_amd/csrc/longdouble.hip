@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "combine.hpp"
+#include "kernel_common.hpp"
 #include "x87.hpp"
 
 namespace osgpu {
@@ -47,9 +47,9 @@ __device__ __forceinline__ void store(unsigned char *p, X80 x)
 template <int OP>
 __device__ __forceinline__ X80 apply(X80 a, X80 b)
 {
-    if (OP == 0) return add(a, b);
-    if (OP == 1) return mul(a, b);
-    if (OP == 5) return less(b, a) ? a : b;      // max: a > b ? a : b
+    if (OP == OP_SUM) return add(a, b);
+    if (OP == OP_PROD) return mul(a, b);
+    if (OP == OP_MAX) return less(b, a) ? a : b;  // max: a > b ? a : b
     return less(a, b) ? a : b;                   // min: a < b ? a : b
 }
 
@@ -139,15 +139,9 @@ __global__ __launch_bounds__(256) void ld_combine_kernel(unsigned char *out, LdI
     }
 }
 
-}  // namespace x87
-
-hipError_t launch_longdouble(int op, void *out, const void *const *srcs, int k, size_t n,
-                             hipStream_t s)
+template <int OP>
+static hipError_t ld_launch(void *out, const void *const *srcs, int k, size_t n, hipStream_t s)
 {
-    if (op != 0 && op != 1 && op != 5 && op != 6) return hipErrorInvalidValue;
-    for (int j = 0; j < k; j++)
-        if (((uintptr_t) srcs[j] & 7) != 0) return hipErrorInvalidValue;
-    if (((uintptr_t) out & 7) != 0) return hipErrorInvalidValue;
     size_t blocks = (n + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     if (blocks == 0) blocks = 1;
@@ -155,40 +149,39 @@ hipError_t launch_longdouble(int op, void *out, const void *const *srcs, int k, 
     int done = 0;
     bool first = true;
     while (done < k) {
-        x87::LdInputs in;
+        LdInputs in;
         int m = 0;
         if (!first) in.p[m++] = (const unsigned char *) out;
-        while (m < x87::kMaxIn && done < k) in.p[m++] = (const unsigned char *) srcs[done++];
+        while (m < kMaxIn && done < k) in.p[m++] = (const unsigned char *) srcs[done++];
         first = false;
         bool aligned16 = ((uintptr_t) out & 15) == 0;
         for (int j = 0; j < m; j++) aligned16 = aligned16 && ((uintptr_t) in.p[j] & 15) == 0;
+        hipError_t e;
         if (aligned16) {  // the usual case: x86-64 long double arrays are 16-B aligned
-            const void *vp[x87::kMaxIn];
+            const void *vp[kMaxIn];
             for (int j = 0; j < m; j++) vp[j] = in.p[j];
-            hipError_t e;
-            switch (op) {
-            case 0: e = x87::ld_vec_launch<0>(m, out, vp, n, s); break;
-            case 1: e = x87::ld_vec_launch<1>(m, out, vp, n, s); break;
-            case 5: e = x87::ld_vec_launch<5>(m, out, vp, n, s); break;
-            default: e = x87::ld_vec_launch<6>(m, out, vp, n, s); break;
-            }
-            if (e != hipSuccess) return e;
-            continue;
+            e = ld_vec_launch<OP>(m, out, vp, n, s);
+        } else {
+            hipLaunchKernelGGL(ld_combine_kernel<OP>, dim3((unsigned) blocks), dim3(256), 0, s,
+                               (unsigned char *) out, in, m, n);
+            e = hipGetLastError();
         }
-        switch (op) {
-        case 0: hipLaunchKernelGGL(x87::ld_combine_kernel<0>, dim3((unsigned) blocks), dim3(256), 0, s,
-                                   (unsigned char *) out, in, m, n); break;
-        case 1: hipLaunchKernelGGL(x87::ld_combine_kernel<1>, dim3((unsigned) blocks), dim3(256), 0, s,
-                                   (unsigned char *) out, in, m, n); break;
-        case 5: hipLaunchKernelGGL(x87::ld_combine_kernel<5>, dim3((unsigned) blocks), dim3(256), 0, s,
-                                   (unsigned char *) out, in, m, n); break;
-        default: hipLaunchKernelGGL(x87::ld_combine_kernel<6>, dim3((unsigned) blocks), dim3(256), 0, s,
-                                    (unsigned char *) out, in, m, n); break;
-        }
-        hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace x87
+
+hipError_t launch_longdouble(int op, void *out, const void *const *srcs, int k, size_t n,
+                             hipStream_t s)
+{
+    for (int j = 0; j < k; j++)
+        if (((uintptr_t) srcs[j] & 7) != 0) return hipErrorInvalidValue;
+    if (((uintptr_t) out & 7) != 0) return hipErrorInvalidValue;
+    return dispatch_ld_op(op, hipErrorInvalidValue, [&](auto o) {
+        return x87::ld_launch<decltype(o)::value>(out, srcs, k, n, s);
+    });
 }
 
 namespace x87 {
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OSGPU_LD_WA
             x[p] = VEC ? unpack(__builtin_nontemporal_load(
                              reinterpret_cast<const u64x2 *>(a.src[p]) + i))
                        : load(a.src[p] + 16 * i);
-        if (OP == 0 || OP == 1) {
+        if (OP == OP_SUM || OP == OP_PROD) {
             team_fold_sum_prod<OP, P>(x, r);
         } else if (P > 2) {
             team_fold_minmax<OP, P>(x, r);
@@ -274,13 +267,9 @@ hipError_t launch_team_longdouble(int op, int P, void *const *dsts, const void *
     }
     size_t blocks = (n + 255) / 256;
     blocks = blocks > 16384 ? 16384 : (blocks ? blocks : 1);
-    switch (op) {
-    case 0: return x87::ld_team_launch<0>(P, vec, a, n, (unsigned) blocks, s);
-    case 1: return x87::ld_team_launch<1>(P, vec, a, n, (unsigned) blocks, s);
-    case 5: return x87::ld_team_launch<5>(P, vec, a, n, (unsigned) blocks, s);
-    case 6: return x87::ld_team_launch<6>(P, vec, a, n, (unsigned) blocks, s);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_ld_op(op, hipErrorInvalidValue, [&](auto o) {
+        return x87::ld_team_launch<decltype(o)::value>(P, vec, a, n, (unsigned) blocks, s);
+    });
 }
 
 }  // namespace osgpu

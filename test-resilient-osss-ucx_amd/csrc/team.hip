@@ -18,20 +18,11 @@
 
 #include <type_traits>
 
-#include "combine.hpp"
-#include "elem_ops.hpp"
+#include "kernel_common.hpp"
 
 #pragma clang fp contract(off)
 
 namespace osgpu {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-union TVec {
-    u32x4 v;
-    T e[16 / sizeof(T)];
-};
 
 template <typename T, int P>
 struct TeamPtrs {
@@ -194,7 +185,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
     using S = TeamShape<T, OP, P, REMOTE>;
     constexpr int U = S::U;
     if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
-        const size_t e = threadIdx.x < head ? threadIdx.x : tail_start + (threadIdx.x - head);
+        const size_t e = edge_index(head, tail_start);
         T x[P], r[P];
 #pragma unroll
         for (int p = 0; p < P; p++) x[p] = a.src[p][e];
@@ -209,13 +200,13 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
     // hold a NaN part (rare; elem_ops.hpp Fast) -- no branch per element, so
     // the tile's loads stay in flight ahead of the folds
     using F = Fast<T, OP>;
-    auto fold_store = [&](TVec<T> (&in)[P], size_t j) __attribute__((always_inline)) {
+    auto fold_store = [&](Vec16<T> (&in)[P], size_t j) __attribute__((always_inline)) {
         if constexpr (ORDERED && S::kPerOutput) {
             // one output at a time: fold, check, store -- only one output
             // vector live beside the inputs
             Rounds<0, P>::run([&](auto qc) {
                 constexpr int q = decltype(qc)::value;
-                TVec<T> out;
+                Vec16<T> out;
                 bool bad = false;
 #pragma unroll
                 for (int w = 0; w < W; w++) {
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
             });
             return;
         }
-        TVec<T> out[P];
+        Vec16<T> out[P];
         bool bad = false;
 #pragma unroll
         for (int w = 0; w < W; w++) {
@@ -276,7 +267,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
         // TeamShape's G (all 4*P at once spills the 8-input complex sum)
         constexpr int G = S::G;
         constexpr int R = U / G;
-        auto load_round = [&](TVec<T> (&in)[G][P], int g) __attribute__((always_inline)) {
+        auto load_round = [&](Vec16<T> (&in)[G][P], int g) __attribute__((always_inline)) {
 #pragma unroll
             for (int u = 0; u < G; u++)
 #pragma unroll
@@ -287,7 +278,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
         };
         if constexpr (S::kPipe) {
             // round r+1's loads go out before round r's stores
-            TVec<T> b0[G][P], b1[G][P];
+            Vec16<T> b0[G][P], b1[G][P];
             load_round(b0, 0);
             Rounds<0, R>::run([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
@@ -300,7 +291,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
         } else {
             Rounds<0, R>::run([&](auto rc) {
                 constexpr int r = decltype(rc)::value;
-                TVec<T> in[G][P];
+                Vec16<T> in[G][P];
                 load_round(in, r);
 #pragma unroll
                 for (int u = 0; u < G; u++) fold_store(in[u], t0 + (size_t) (r * G + u) * kTeamBlock);
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(kTeamBlock) void team_vec_kernel(TeamPtrs<T, P> a, 
     for (int u = 0; u < U; u++) {
         const size_t j = t0 + (size_t) u * kTeamBlock;
         if (j < nvec) {
-            TVec<T> in[P];
+            Vec16<T> in[P];
 #pragma unroll
             for (int p = 0; p < P; p++)
                 in[p].v = __builtin_nontemporal_load(
@@ -352,7 +343,7 @@ __global__ __launch_bounds__(64 * P) void team_lds_kernel(TeamPtrs<T, P> a, size
     constexpr int V = 64 * U;  // vectors per member per tile
     __shared__ u32x4 tile[P][V];
     if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
-        const size_t e = threadIdx.x < head ? threadIdx.x : tail_start + (threadIdx.x - head);
+        const size_t e = edge_index(head, tail_start);
         T x[P], r[P];
 #pragma unroll
         for (int p = 0; p < P; p++) x[p] = a.src[p][e];
@@ -387,7 +378,7 @@ __global__ __launch_bounds__(64 * P) void team_lds_kernel(TeamPtrs<T, P> a, size
 #pragma unroll
             for (int u = u0; u < u1; u++) {
                 if (!whole && base + u * 64 + lane >= nvec) continue;
-                TVec<T> in[P], out;
+                Vec16<T> in[P], out;
 #pragma unroll
                 for (int p = 0; p < P; p++) in[p].v = tile[p][u * 64 + lane];
                 bool bad = false;
@@ -460,14 +451,12 @@ static hipError_t team_launch_p(void *const *dsts, const void *const *srcs, size
     // floating-point op, min/max included (NaN, signed zero), is not
     constexpr bool ORDERED = !std::is_integral<T>::value;
     TeamPtrs<T, P> a;
-    const uintptr_t phase = (uintptr_t) srcs[0] & 15;
-    bool same = (phase % sizeof(T)) == 0;
     for (int p = 0; p < P; p++) {
         a.src[p] = static_cast<const T *>(srcs[p]);
         a.dst[p] = static_cast<T *>(dsts[p]);
-        same = same && (((uintptr_t) srcs[p] & 15) == phase) && (((uintptr_t) dsts[p] & 15) == phase);
     }
-    if (!same) {
+    const VecSplit vs = vec_split(sizeof(T), n, srcs, P, dsts, P);
+    if (!vs.vec) {
         size_t blocks = tl.blocks((n + kTeamBlock - 1) / kTeamBlock);
         blocks = blocks > 8192 ? 8192 : blocks;
         hipLaunchKernelGGL((team_scalar_kernel<T, OP, P, ORDERED>), dim3((unsigned) blocks),
@@ -475,31 +464,20 @@ static hipError_t team_launch_p(void *const *dsts, const void *const *srcs, size
         return hipGetLastError();
     }
     constexpr int W = 16 / sizeof(T);
-    size_t head = phase ? (16 - phase) / sizeof(T) : 0;
-    if (head > n) head = n;
-    const size_t nvec = (n - head) / W;
-    const size_t tail_start = head + nvec * W;
     // the unaligned head and the tail: member 0's first workgroup
-    const int nedge = tl.k == 0 ? (int) (head + (n - tail_start)) : 0;
+    const int nedge = tl.k == 0 ? vs.nedge : 0;
     // tiles of V vectors, this member's every tl.m-th one, one per workgroup
-    // of `threads`; at most max_launch_threads() per launch (combine.hpp):
-    // runs of tiles that are whole multiples of tl.m, so tile t of a run is
-    // still this member's when t % tl.m == tl.k; the first launch takes the
-    // edges, the others shifted pointers
+    // of `threads`, in runs that are whole multiples of tl.m
+    // (for_each_tile_run): the first launch takes the edges, the others
+    // shifted pointers
     auto launch = [&](size_t V, unsigned threads, auto kernel) -> hipError_t {
-        size_t tiles = (nvec + V - 1) / V;
-        if (tiles == 0) tiles = 1;
-        const size_t lim = max_launch_threads() / threads;
-        const size_t run = (lim ? lim : 1) * tl.m;
-        for (size_t t0 = 0; t0 < tiles; t0 += run) {
-            const size_t nt = tiles - t0 < run ? tiles - t0 : run;
-            const size_t nv = nvec - t0 * V < nt * V ? nvec - t0 * V : nt * V;
+        return for_each_tile_run(vs.nvec, V, threads, tl.m, [&](size_t t0, size_t nt, size_t nv) {
             const size_t blocks = tl.blocks(nt);
             if (t0 == 0) {
-                hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, s, a, nv, head,
-                                   tail_start, nedge, tl.m, tl.k);
+                hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, s, a, nv,
+                                   vs.head, vs.tail_start, nedge, tl.m, tl.k);
             } else {
-                const size_t off = head + t0 * V * W;
+                const size_t off = vs.head + t0 * V * W;
                 TeamPtrs<T, P> c;
                 for (int p = 0; p < P; p++) {
                     c.src[p] = a.src[p] + off;
@@ -508,10 +486,8 @@ static hipError_t team_launch_p(void *const *dsts, const void *const *srcs, size
                 hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, s, c, nv,
                                    (size_t) 0, (size_t) 0, 0, tl.m, tl.k);
             }
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            return hipGetLastError();
+        });
     };
     if constexpr (S::kLds) {
         constexpr int UL = S::kLdsU;
@@ -548,59 +524,17 @@ static hipError_t team_launch_op(int P, void *const *d, const void *const *sr, s
     return hipErrorInvalidValue;
 }
 
-#define TEAM_CASE(OPC)                                                         \
-    case OPC: return team_launch_op<T, OPC>(P, d, sr, n, tl, s);
-
-template <typename T>
-static hipError_t team_int(int op, int P, void *const *d, const void *const *sr, size_t n,
-                           Tiles tl, hipStream_t s)
-{
-    switch (op) {
-        TEAM_CASE(OP_SUM) TEAM_CASE(OP_PROD) TEAM_CASE(OP_AND) TEAM_CASE(OP_OR)
-        TEAM_CASE(OP_XOR) TEAM_CASE(OP_MAX) TEAM_CASE(OP_MIN)
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t team_real(int op, int P, void *const *d, const void *const *sr, size_t n,
-                            Tiles tl, hipStream_t s)
-{
-    switch (op) {
-        TEAM_CASE(OP_SUM) TEAM_CASE(OP_PROD) TEAM_CASE(OP_MAX) TEAM_CASE(OP_MIN)
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T>
-static hipError_t team_cplx(int op, int P, void *const *d, const void *const *sr, size_t n,
-                            Tiles tl, hipStream_t s)
-{
-    switch (op) {
-        TEAM_CASE(OP_SUM) TEAM_CASE(OP_PROD)
-    }
-    return hipErrorInvalidValue;
-}
-
 hipError_t launch_team_tiles(int type, int op, int P, void *const *dsts, const void *const *srcs,
                              size_t n, int m, int k, hipStream_t s, bool remote)
 {
     if (P < 2 || P > kMaxTeam || m < 1 || k < 0 || k >= m) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const Tiles tl{(unsigned) m, (unsigned) k, remote};
-    switch (type) {
-    case T_SHORT: return team_int<int16_t>(op, P, dsts, srcs, n, tl, s);
-    case T_INT: return team_int<int32_t>(op, P, dsts, srcs, n, tl, s);
-    case T_LONG:
-    case T_LONGLONG: return team_int<int64_t>(op, P, dsts, srcs, n, tl, s);
-    case T_FLOAT: return team_real<float>(op, P, dsts, srcs, n, tl, s);
-    case T_DOUBLE: return team_real<double>(op, P, dsts, srcs, n, tl, s);
-    case T_COMPLEXF: return team_cplx<cfloat>(op, P, dsts, srcs, n, tl, s);
-    case T_COMPLEXD: return team_cplx<cdouble>(op, P, dsts, srcs, n, tl, s);
-    case T_LONGDOUBLE:
+    if (type == T_LONGDOUBLE)
         return m == 1 ? launch_team_longdouble(op, P, dsts, srcs, n, s) : hipErrorNotSupported;
-    }
-    return hipErrorInvalidValue;
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return team_launch_op<typename decltype(t)::type, decltype(o)::value>(P, dsts, srcs, n, tl, s);
+    });
 }
 
 hipError_t launch_team(int type, int op, int P, void *const *dsts, const void *const *srcs,

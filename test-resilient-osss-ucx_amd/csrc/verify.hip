@@ -11,7 +11,7 @@
 #include <stdint.h>
 #include <stddef.h>
 
-#include "combine.hpp"
+#include "kernel_common.hpp"
 
 namespace osgpu {
 
@@ -19,7 +19,6 @@ namespace {
 
 constexpr int kVBlock = 256;
 constexpr int kWaves = kVBlock / 64;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z)  // splitmix64 finaliser
 {

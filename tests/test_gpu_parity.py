@@ -541,7 +541,7 @@ def test_team_combine_launcher(torch_cuda, t, op, P, shift):
         assert (outs[q][off + n * s:].cpu().numpy() == 0x5A).all()
 
 
-REMOTE_CASES = [(t, op, P) for P in (2, 5, 8)
+REMOTE_CASES = [(t, op, P) for P in (2, 5, 6, 7, 8)
                 for t, op in (("double", "sum"), ("float", "prod"), ("double", "min"),
                               ("float", "max"), ("int", "sum"), ("long", "xor"),
                               ("short", "prod"), ("complexf", "sum"), ("complexd", "prod"))]
@@ -668,12 +668,13 @@ def test_combine_multi_launch(torch_cuda, small_launches, t, k):
             assert bad.size == 0, (t, k, n, shift, bad[:8] // s)
 
 
-@pytest.mark.parametrize("P", [2, 3, 4, 5, 8])
+@pytest.mark.parametrize("P", [2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("t,op", [("double", "sum"), ("int", "xor"), ("float", "max"),
                                   ("complexf", "prod"), ("short", "min")])
 def test_team_multi_launch(torch_cuda, small_launches, P, t, op):
-    """The team kernels (LDS form at 2-4 and, real types, 8 members; register
-    form otherwise) over many launches (team.hip team_launch_p): ragged n,
+    """The team kernels (LDS form at 2-4 members and, for real types other
+    than floating-point max/min, at 5, 6 and 8; register form otherwise)
+    over many launches (team.hip team_launch_p): ragged n,
     one 16-byte phase for every array, every member's result bit-exact
     against its own fold order."""
     torch = torch_cuda

@@ -7,7 +7,8 @@ launch block on the same arrays.  Not part of the product.
   python tools/combine_variants.py run     (on the GPU box)
 
 Variants: CV_VARIANTS="name=-DFLAG=V -DFLAG2=W;name2=..." (default: the
-tree's build vs OSGPU_COMBINE_G8=2 and =1).  Per (type, K): CV_ROUNDS rounds
+tree's build vs OSGPU_COMBINE_LDS_U2=4, the one knob combine.hip still
+reads).  Per (type, K): CV_ROUNDS rounds
 of (for each variant: a HIP-event span over REPS launches), the median per
 variant, (K + 1) * n * s bytes per launch; every variant's output must equal
 the first variant's.
@@ -27,7 +28,7 @@ OTHERS = ["team.o", "fused.o", "verify.o", "longdouble.o", "copy.o", "runtime.o"
 
 
 def variants():
-    spec = os.environ.get("CV_VARIANTS", "base=;g2=-DOSGPU_COMBINE_G8=2;g1=-DOSGPU_COMBINE_G8=1")
+    spec = os.environ.get("CV_VARIANTS", "base=;u4=-DOSGPU_COMBINE_LDS_U2=4")
     out = {}
     for item in filter(None, spec.split(";")):
         name, flags = item.split("=", 1)

@@ -31,15 +31,11 @@ FL = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"
       "-fno-fast-math"]
 VARIANTS = {
     "r03": ("git:5c84853", []),                       # round 3's shipped team kernel
-    "tree": (None, ["-DOSGPU_TEAM_PIPE=0", "-DOSGPU_TEAM_PEROUT=0"]),  # r04 shape, r03 order
-    "gh1": (None, ["-DOSGPU_TEAM_GH=1", "-DOSGPU_TEAM_PIPE=0", "-DOSGPU_TEAM_PEROUT=0"]),
-    "pipe_g1": (None, ["-DOSGPU_TEAM_PIPE=1", "-DOSGPU_TEAM_G8=1", "-DOSGPU_TEAM_GH=1",
-                       "-DOSGPU_TEAM_PEROUT=0"]),
-    "perout": (None, ["-DOSGPU_TEAM_PEROUT=1", "-DOSGPU_TEAM_PIPE=0"]),
+    # (the round-4/5 variants of the pipelined / per-output / round-size
+    # macros went with those macros: team.hip reads none of them any more)
     "tree2": (None, ["-DOSGPU_TEAM_LDS_MIN_P=9"]),    # register form at every P
     "final": (None, []),                              # the tree's defaults
     "final2": (None, []),                             # duplicate build (control)
-    "g8_4": (None, ["-DOSGPU_TEAM_G8=4"]),            # 8 members: all 4 x 8 vectors in flight
     # (a two-half LDS tile, OSGPU_TEAM_LDS_SPLIT, measured equal to one and
     # was removed: profiles/r04_team_place_4.jsonl)
     "lds8": (None, ["-DOSGPU_TEAM_LDS_MAX_P=8"]),      # LDS form at 3-8 members
@@ -51,8 +47,6 @@ VARIANTS = {
     "lds2": (None, ["-DOSGPU_TEAM_LDS_MIN_P=2"]),
     "lds5u2": (None, ["-DOSGPU_TEAM_LDS_MIN_P=5", "-DOSGPU_TEAM_LDS_U=2"]),
     "lds5u8": (None, ["-DOSGPU_TEAM_LDS_MIN_P=5", "-DOSGPU_TEAM_LDS_U=8"]),
-    "u8_pipe_g2": (None, ["-DOSGPU_TEAM_PIPE=1", "-DOSGPU_TEAM_U8=8", "-DOSGPU_TEAM_G8=2",
-                          "-DOSGPU_TEAM_GH=1", "-DOSGPU_TEAM_PEROUT=0"]),
 }
 if os.environ.get("TV_BUILD"):
     VARIANTS = {k: v for k, v in VARIANTS.items() if k in os.environ["TV_BUILD"].split(",")}

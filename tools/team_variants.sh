@@ -1,5 +1,5 @@
 #!/bin/bash
-# team-kernel variants (tools/build_variants.sh) against the shipped build,
+# team-kernel variants (libraries under tools/variants/) against the shipped build,
 # one box, interleaved: team_type_sweep.py for a few types at P = 4 and 8
 mkdir -p gpurun_out
 for rep in 1 2; do
