@@ -63,6 +63,25 @@ struct CopySeg {
     size_t bytes;
 };
 hipError_t launch_copy(const CopySeg *segs, int nseg, hipStream_t s);
+// Strided element copy of up to kMaxCopySegs independent segments in one
+// launch per form (copy.hip): the data movement of alltoalls.  For k < nelems,
+//   dst[k * dst_stride] = src[k * sst]     (elements of elem_bytes = 4 or 8;
+// strides in elements, >= 1; pointers aligned to elem_bytes; sources may be
+// peer HBM).  Nothing between the strided elements is written.  Empty
+// segments are skipped; more than kMaxCopySegs is an error (callers batch).
+struct StridedSeg {
+    const void *src;
+    void *dst;
+    size_t nelems;
+    ptrdiff_t sst, dst_stride;
+};
+hipError_t launch_strided_copy(int elem_bytes, const StridedSeg *segs, int nseg, hipStream_t s);
+// Launch shape of one form of the strided kernel (0 gather, 1 scatter, 2
+// both strided; -1 all): u elements / vectors in flight per lane (2, 4 or
+// 8), nt = 1 non-temporal accesses on the strided side.  u <= 0 restores
+// the shipped shape.  For tools/strided_rate.py's in-process A/B only
+// (osgpu_test_strided_shape); false for a shape that is not compiled.
+bool set_strided_shape(int form, int u, int nt);
 // Host fold of small host-heap calls (host_fold.hip): acc[i] = op(acc[i],
 // in[i]) for i < n with the kernels' element ops compiled for the host
 bool host_fold_supported(int type, int op);

@@ -1585,6 +1585,52 @@ int osgpu_copy(void *const *dsts, const void *const *srcs, const size_t *bytes, 
     return OSGPU_OK;
 }
 
+int osgpu_copy_strided(int elem_bytes, void *const *dsts, const ptrdiff_t *dst_strides,
+                       const void *const *srcs, const ptrdiff_t *src_strides,
+                       const size_t *nelems, int n, void *hip_stream)
+{
+    bool ok = (elem_bytes == 4 || elem_bytes == 8) && n >= 0 &&
+              (n == 0 || (dsts && dst_strides && srcs && src_strides && nelems));
+    for (int i = 0; ok && i < n; i++)
+        ok = dst_strides[i] >= 1 && src_strides[i] >= 1 &&
+             ((uintptr_t) dsts[i] | (uintptr_t) srcs[i]) % (uintptr_t) elem_bytes == 0;
+    if (!ok) {
+        set_err("osgpu_copy_strided: bad arguments (elem_bytes 4 or 8, strides >= 1, pointers "
+                "aligned to elem_bytes)");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_copy_strided");
+    for (int i = 0; i < n; i += osgpu::kMaxCopySegs) {
+        osgpu::StridedSeg seg[osgpu::kMaxCopySegs];
+        const int m = n - i < osgpu::kMaxCopySegs ? n - i : osgpu::kMaxCopySegs;
+        for (int j = 0; j < m; j++)
+            seg[j] = {srcs[i + j], dsts[i + j], nelems[i + j], src_strides[i + j], dst_strides[i + j]};
+        hipError_t e = osgpu::launch_strided_copy(elem_bytes, seg, m, st);
+        if (e != hipSuccess) {
+            set_err("osgpu_copy_strided: %s", hipGetErrorString(e));
+            return OSGPU_EHIP;
+        }
+    }
+    return OSGPU_OK;
+}
+
+// Test hook (tools/strided_rate.py's in-process A/B): the launch shape of
+// the strided kernel's forms (combine.hpp set_strided_shape).  Not in the
+// public header and refused unless the process runs with OSGPU_TEST_HOOKS=1.
+int osgpu_test_strided_shape(int form, int u, int nt)
+{
+    const char *on = getenv("OSGPU_TEST_HOOKS");
+    if (!on || strcmp(on, "1")) {
+        set_err("osgpu_test_strided_shape: test hooks are off (OSGPU_TEST_HOOKS=1 enables them)");
+        return OSGPU_EINVAL;
+    }
+    if (!osgpu::set_strided_shape(form, u, nt)) {
+        set_err("osgpu_test_strided_shape: form -1..2, u 2, 4 or 8 (<= 0: the shipped shape)");
+        return OSGPU_EINVAL;
+    }
+    return OSGPU_OK;
+}
+
 // result words of the verification launchers, per thread and device
 struct VerifyBuf {
     int device = -1;

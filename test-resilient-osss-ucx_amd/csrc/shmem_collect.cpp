@@ -1,7 +1,7 @@
 // shmem_collect.cpp -- the data-movement collectives on the reduce path's
 // machinery: broadcast32/64, collect32/64,
-// fcollect32/64, alltoall32/64, same signatures as the reference
-// (include/shmem/api.h:2415-2450).
+// fcollect32/64, alltoall32/64, alltoalls32/64, same signatures as the
+// reference (include/shmem/api.h:2415-2460).
 //
 // Reference algorithms (bytes move with UCX puts/gets, one PE at a time):
 //   broadcast  src/shmemc/broadcast.c:29-42 (linear: barrier, every non-root
@@ -15,7 +15,28 @@
 //              block vpe = (me - PE_start) >> logPE_stride (:27) of every
 //              target (:32-38), barrier (:39);
 //   alltoall   src/alltoall.c:59-82: block i of my target <- a block of PE
-//              i's source (gets, no synchronisation at all).
+//              i's source (gets, no synchronisation at all);
+//   alltoalls  src/alltoall.c:26-55: the same with element strides dst /
+//              sst, one shmem_iget per member, i.e. one UCX get PER ELEMENT
+//              (src/putget.h:185-207).
+//
+// alltoalls follows OpenSHMEM 1.4 -- target[(j*nelems + k) * dst] =
+// source of member j [(me_idx*nelems + k) * sst], strides in elements --
+// where the reference's literal text differs from it (as alltoall already
+// does for the first point):
+//   - src/alltoall.c:46 indexes the source block by proc.rank, not by the
+//     caller's index in the active set;
+//   - src/alltoall.c:45-46 computes tidx / sidx in int;
+//   - the sized iget it calls advances by tst / sst BYTES per element
+//     (src/putget.h:204-205), so at stride 1 its 4-byte gets overlap.
+// dst == sst == 1 is alltoall and runs as K_ALLTOALL on every path below.
+// A strided call has two paths only: COPY on device heaps (copy.hip's
+// strided kernel between the same two barriers; a target span that overlaps
+// my source span, interleaved layouts included, is gathered into packed
+// scratch and scattered after the exit barrier) and GETMEM on host heaps
+// (one getmem of each peer's block span per chunk, then a host strided
+// loop).  No FUSED, STAGED (its D2H of a strided target would have to
+// preserve the gaps) or RCCL form: OSGPU_HOST_PATH=staged takes GETMEM.
 //
 // Here every PE PULLS all the pieces of its own target in one launch of
 // copy.hip's kernel (16-byte streaming loads from local or peer HBM):
@@ -64,15 +85,17 @@ using namespace osgpu::rt;
 
 thread_local int t_last_coll = OSGPU_RAN_NONE;
 
-enum Kind { K_BCAST, K_COLLECT, K_FCOLLECT, K_ALLTOALL };
+enum Kind { K_BCAST, K_COLLECT, K_FCOLLECT, K_ALLTOALL, K_ALLTOALLS };
 
 constexpr int kCountWord = 8;  // pSync word carrying nelems during collect
 
 // one piece of my target: bytes [src_off, src_off + len) of the source of the
-// PE at active-set index `from`, to byte dst_off of my target
+// PE at active-set index `from`, to byte dst_off of my target.  alltoalls:
+// len / esz elements, sst elements apart from src_off, dst apart from dst_off
 struct Piece {
     int from;
     size_t src_off, len, dst_off;
+    ptrdiff_t sst = 1, dst = 1;
 };
 
 struct CCall : Coll {
@@ -83,9 +106,10 @@ struct CCall : Coll {
     size_t nelems = 0;
     int root = 0;                  // broadcast: active-set index of the root
     int idx = -1;                  // my active-set index
-    std::vector<size_t> src_len;   // bytes of every member's source
+    ptrdiff_t dst = 1, sst = 1;    // alltoalls: element strides of target / source
+    std::vector<size_t> src_len;   // bytes of every member's source (alltoalls: its extent)
     std::vector<Piece> pieces;     // what my target receives
-    size_t out_bytes = 0;          // extent of my target that is written
+    size_t out_bytes = 0;          // extent of my target that is written (alltoalls: spanned)
 };
 
 bool overlap2(const void *a, size_t na, const void *b, size_t nb)
@@ -146,6 +170,15 @@ void plan(CCall &c)
             c.pieces.push_back({i, (size_t) c.idx * nb, nb, (size_t) i * nb});
         c.out_bytes = (size_t) P * nb;
         break;
+    case K_ALLTOALLS: {  // extents: ((P * nelems - 1) * stride + 1) elements
+        const size_t last = (size_t) P * c.nelems - 1;
+        c.src_len.assign(P, (last * (size_t) c.sst + 1) * c.esz);
+        for (int i = 0; i < P; i++)
+            c.pieces.push_back({i, (size_t) c.idx * nb * (size_t) c.sst, nb,
+                                (size_t) i * nb * (size_t) c.dst, c.sst, c.dst});
+        c.out_bytes = (last * (size_t) c.dst + 1) * c.esz;
+        break;
+    }
     }
 }
 
@@ -398,6 +431,42 @@ void run_copy(const CCall &c, const std::vector<const char *> &src, bool counts_
     }
 }
 
+// alltoalls on device heaps: one StridedSeg per member through copy.hip's
+// strided kernel, between run_copy's two barriers.  My target's span
+// overlapping my source's span (the same object, or the two interleaved in
+// one array) counts as an overlap: the pieces are gathered into packed
+// scratch and scattered to the target once every reader of my source is done.
+void run_copy_strided(const CCall &c, const std::vector<const char *> &src)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const size_t packed = (size_t) c.PE_size * c.nelems * c.esz;
+    const bool scratch = overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
+    char *out = scratch ? (char *) device_scratch(c.name, c.me, packed) : (char *) c.target;
+    std::vector<osgpu::StridedSeg> segs;
+    for (const Piece &p : c.pieces)
+        segs.push_back({src[p.from] + p.src_off,
+                        scratch ? out + p.dst_off / (size_t) p.dst : out + p.dst_off,
+                        p.len / c.esz, p.sst, scratch ? 1 : p.dst});
+    t_last_coll = OSGPU_RAN_COPY;
+    DBG("%s PE %d: strided copy path, %zu pieces of %zu elements, dst %td sst %td%s", c.name,
+        c.me, segs.size(), c.nelems, c.dst, c.sst, scratch ? " (scratch)" : "");
+    entry_sync(c.name);
+    barrier(c);  // every source ready
+    for (size_t i = 0; i < segs.size(); i += osgpu::kMaxCopySegs) {
+        const int n = (int) std::min(segs.size() - i, (size_t) osgpu::kMaxCopySegs);
+        hipError_t e = osgpu::launch_strided_copy((int) c.esz, segs.data() + i, n, st);
+        if (e != hipSuccess) fatal(c.name, "strided copy launch: %s", hipGetErrorString(e));
+    }
+    stream_wait(c.name, st);
+    barrier(c);  // every reader of my source is done
+    if (scratch) {
+        const osgpu::StridedSeg g = {out, c.target, (size_t) c.PE_size * c.nelems, 1, c.dst};
+        hipError_t e = osgpu::launch_strided_copy((int) c.esz, &g, 1, st);
+        if (e != hipSuccess) fatal(c.name, "strided copy launch: %s", hipGetErrorString(e));
+        stream_wait(c.name, st);
+    }
+}
+
 // ------------------------------------------------------------ RCCL (device)
 
 bool rccl_whole_job(const CCall &c)
@@ -519,12 +588,64 @@ void run_getmem(const CCall &c)
     }
 }
 
+// cnt elements of esz (4 or 8) bytes, ss / ds elements apart
+void host_strided_copy(size_t esz, void *d, ptrdiff_t ds, const void *s, ptrdiff_t ss, size_t cnt)
+{
+    if (esz == 4) {
+        for (size_t k = 0; k < cnt; k++) ((uint32_t *) d)[k * ds] = ((const uint32_t *) s)[k * ss];
+    } else {
+        for (size_t k = 0; k < cnt; k++) ((uint64_t *) d)[k * ds] = ((const uint64_t *) s)[k * ss];
+    }
+}
+
+// alltoalls on host heaps: per peer one getmem of its block's span
+// (((nelems - 1) * sst + 1) elements, in chunks of the GETMEM chunk size)
+// into a temporary, then a host strided loop into the target -- a packed
+// temporary target when my target's span overlaps my source's, scattered
+// after the exit barrier (the gaps of the target are never written).
+void run_getmem_strided(const CCall &c)
+{
+    t_last_coll = OSGPU_RAN_GETMEM;
+    if (!c.ops.getmem) fatal(c.name, "host-memory arguments need shmem_getmem");
+    const size_t total = (size_t) c.PE_size * c.nelems;
+    const bool tmp = overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
+    char *result = tmp ? (char *) malloc(total * c.esz) : (char *) c.target;
+    if (tmp && !result) fatal(c.name, "out of memory for the temporary target");
+    const ptrdiff_t rst = tmp ? 1 : c.dst;
+    const size_t pitch = (size_t) c.sst * c.esz;  // bytes from one source element to the next
+    const size_t per = std::max<size_t>(host_chunk_bytes() / pitch, 1);  // elements per getmem
+    std::vector<char> buf;
+    for (const Piece &p : c.pieces) {
+        const char *s = (const char *) c.source + p.src_off;
+        char *d = result + (tmp ? p.dst_off / (size_t) p.dst : p.dst_off);
+        if (p.from == c.idx) {
+            host_strided_copy(c.esz, d, rst, s, c.sst, c.nelems);
+            continue;
+        }
+        for (size_t k0 = 0; k0 < c.nelems; k0 += per) {
+            const size_t cnt = std::min(per, c.nelems - k0);
+            buf.resize((cnt - 1) * pitch + c.esz);
+            c.ops.getmem(buf.data(), s + k0 * pitch, buf.size(), c.pe_at(p.from));
+            host_strided_copy(c.esz, d + k0 * (size_t) rst * c.esz, rst, buf.data(), c.sst, cnt);
+        }
+    }
+    barrier(c);  // every reader of my source is done
+    if (tmp) {
+        host_strided_copy(c.esz, c.target, c.dst, result, 1, total);
+        free(result);
+    }
+}
+
 // ------------------------------------------------------------ dispatcher
 
 void collective(const char *name, Kind kind, size_t esz, void *target, const void *source,
                 size_t nelems, int PE_root, int PE_start, int logPE_stride, int PE_size,
-                long *pSync)
+                long *pSync, ptrdiff_t dst = 1, ptrdiff_t sst = 1)
 {
+    if (kind == K_ALLTOALLS) {
+        if (dst < 1 || sst < 1) fatal(name, "strides must be at least 1 (dst %td, sst %td)", dst, sst);
+        if (dst == 1 && sst == 1) kind = K_ALLTOALL;  // every path of the contiguous plan
+    }
     CCall c;
     static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
     c.kind = kind;
@@ -533,6 +654,8 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
     c.esz = esz;
     c.nelems = nelems;
     c.root = PE_root;
+    c.dst = dst;
+    c.sst = sst;
     c.idx = c.index_of(c.me);
     if (c.idx < 0) fatal(name, "PE %d is not in the active set", c.me);
     if (kind == K_BCAST && (PE_root < 0 || PE_root >= PE_size))
@@ -591,12 +714,19 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
         const int hp = host_path();
         const bool force_getmem = hp == OSGPU_HOST_GETMEM;
         const bool force_staged = hp == OSGPU_HOST_STAGED;
-        StageSet *S = force_getmem ? nullptr : stage_setup(c);
+        // a strided call has no STAGED form (the D2H of a strided target
+        // would have to preserve the gaps): GETMEM under every setting
+        const bool strided = kind == K_ALLTOALLS;
+        if (strided && force_staged)
+            DBG("%s PE %d: no STAGED form of a strided call, taking GETMEM", name, c.me);
+        StageSet *S = force_getmem || strided ? nullptr : stage_setup(c);
         if (S && force_staged && !counts_done && run_fused_staged_copy(c, *S)) return;
         if (!counts_done) barrier(c);  // sources ready
         const bool small = shared_bytes(c) <= fused_max_bytes();
         if (S && (force_staged || (!small && (S->ndev == c.PE_size || c.PE_size == 1))))
             run_staged(c, *S);
+        else if (strided)
+            run_getmem_strided(c);
         else
             run_getmem(c);
         barrier(c);
@@ -609,7 +739,12 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
     if (cur != dt) HIPCHK(name, hipSetDevice(dt));
     const int mode = path_mode();
     std::vector<const char *> src;
-    if (mode != OSGPU_PATH_RCCL && device_sources(c, src)) {
+    if (kind == K_ALLTOALLS) {  // COPY only: no FUSED or RCCL form
+        if (!device_sources(c, src))
+            fatal(name, "device-resident arguments need every active PE's device heap "
+                        "registered (osgpu_heap_register)");
+        run_copy_strided(c, src);
+    } else if (mode != OSGPU_PATH_RCCL && device_sources(c, src)) {
         run_copy(c, src, counts_done);
     } else if ((mode == OSGPU_PATH_AUTO || mode == OSGPU_PATH_RCCL) && !counts_done &&
                rccl_whole_job(c)) {
@@ -675,3 +810,19 @@ extern "C" int osgpu_last_coll_path(void) { return t_last_coll; }
 
 OSGPU_DEFINE_COLL(32, 4)
 OSGPU_DEFINE_COLL(64, 8)
+
+// src/alltoall.c:19-23 (weak) and :26-55
+#define OSGPU_DEFINE_ALLTOALLS(_bits, _bytes)                                              \
+    extern "C" void pshmem_alltoalls##_bits(void *target, const void *source, ptrdiff_t dst, \
+                                            ptrdiff_t sst, size_t nelems, int PE_start,    \
+                                            int logPE_stride, int PE_size, long *pSync)    \
+    {                                                                                      \
+        collective("shmem_alltoalls" #_bits, K_ALLTOALLS, _bytes, target, source, nelems,  \
+                   0, PE_start, logPE_stride, PE_size, pSync, dst, sst);                   \
+    }                                                                                      \
+    extern "C" void shmem_alltoalls##_bits(void *, const void *, ptrdiff_t, ptrdiff_t,     \
+                                           size_t, int, int, int, long *)                  \
+        OSGPU_ALIAS(alltoalls##_bits);
+
+OSGPU_DEFINE_ALLTOALLS(32, 4)
+OSGPU_DEFINE_ALLTOALLS(64, 8)

@@ -49,6 +49,8 @@ assert len(ENTRY_POINTS) == 44
 # data-movement collectives on the same machinery (include/osgpu_reduce.h Part 1b)
 COLL_KINDS = ["broadcast", "collect", "fcollect", "alltoall"]
 COLL_ENTRY_POINTS = [f"shmem_{k}{b}" for k in COLL_KINDS for b in (32, 64)]
+# the strided all-to-all (dst / sst element strides ahead of nelems)
+STRIDED_COLL_ENTRY_POINTS = [f"shmem_alltoalls{b}" for b in (32, 64)]
 
 
 class PeOps(ctypes.Structure):
@@ -111,6 +113,12 @@ def load() -> ctypes.CDLL:
             else:
                 f.argtypes = [vp, vp, sz_t, i, i, i, lp]
             f.restype = None
+    pd = ctypes.c_ssize_t
+    for name in STRIDED_COLL_ENTRY_POINTS:
+        for pfx in ("", "p"):
+            f = getattr(L, pfx + name)
+            f.argtypes = [vp, vp, pd, pd, sz_t, i, i, i, lp]
+            f.restype = None
     L.osgpu_set_pe_ops.argtypes = [vp]
     L.osgpu_heap_register.argtypes = [i, vp, sz]
     L.osgpu_heap_register_segment.argtypes = [i, i, vp, sz]
@@ -133,6 +141,7 @@ def load() -> ctypes.CDLL:
     L.osgpu_get_stream.restype = vp
     L.osgpu_combine.argtypes = [i, i, vp, vp, i, sz, vp]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
+    L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
     L.osgpu_team_combine_shape.argtypes = [i, i, i, vp, vp, sz, vp, i]
     L.osgpu_build_id.restype = ctypes.c_char_p
@@ -319,6 +328,29 @@ def copy(dsts, srcs, nbytes, stream: int | None = None):
         raise RuntimeError(f"osgpu_copy = {rc}: {L.osgpu_last_error().decode()}")
 
 
+def copy_strided(elem_bytes: int, dsts, dst_strides, srcs, src_strides, nelems,
+                 stream: int | None = None, check: bool = True) -> int:
+    """Enqueue the strided copy kernel: dsts[i][k * dst_strides[i]] =
+    srcs[i][k * src_strides[i]] for k < nelems[i], elements of elem_bytes.
+    Returns the status; check=True raises on a non-zero one."""
+    L = load()
+    n = len(dsts)
+    rc = L.osgpu_copy_strided(elem_bytes, (ctypes.c_void_p * n)(*dsts),
+                              (ctypes.c_ssize_t * n)(*dst_strides),
+                              (ctypes.c_void_p * n)(*srcs),
+                              (ctypes.c_ssize_t * n)(*src_strides),
+                              (ctypes.c_size_t * n)(*nelems), n, stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_copy_strided = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
+
+
+def coll_strided(bits: int):
+    """The ctypes function shmem_alltoalls<bits>(target, source, dst, sst,
+    nelems, PE_start, logPE_stride, PE_size, pSync)."""
+    return getattr(load(), f"shmem_alltoalls{bits}")
+
+
 def coll(kind: str, bits: int):
     """The ctypes function shmem_<kind><bits> (broadcast/collect/fcollect/alltoall)."""
     return getattr(load(), f"shmem_{kind}{bits}")
@@ -349,6 +381,6 @@ def header_symbols(path: str = HEADER):
     names = set(re.findall(r"^\s*(?:const\s+)?[A-Za-z_][\w\s\*]*?\b(osgpu_\w+)\s*\(",
                            src, re.M))
     for pfx in ("shmem_", "pshmem_"):
-        for e in ENTRY_POINTS + COLL_ENTRY_POINTS:
+        for e in ENTRY_POINTS + COLL_ENTRY_POINTS + STRIDED_COLL_ENTRY_POINTS:
             names.add(pfx + e[len("shmem_"):])
     return sorted(names)
