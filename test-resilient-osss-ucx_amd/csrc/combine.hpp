@@ -10,10 +10,11 @@ namespace osgpu {
 // tools/tune_combine.hip)
 constexpr int kUK2 = 4, kUK4 = 4, kUK8 = 4;
 
-// type codes (same numbering as include/osgpu_reduce.h OSGPU_T_*)
+// type codes (same numbering as include/osgpu_reduce.h OSGPU_T_*); T_HALF
+// and T_BFLOAT16 are the extension types (16-bit patterns, elem_ops.hpp)
 enum TypeCode {
     T_SHORT = 0, T_INT, T_LONG, T_LONGLONG, T_FLOAT, T_DOUBLE, T_LONGDOUBLE,
-    T_COMPLEXF, T_COMPLEXD, T_NTYPES
+    T_COMPLEXF, T_COMPLEXD, T_HALF, T_BFLOAT16, T_NTYPES
 };
 
 // out[i] = fold(op, srcs[0][i], srcs[1][i], ..., srcs[k-1][i]) for i < n,

@@ -198,6 +198,130 @@ template <> struct Elem<cfloat, OP_PROD> {
     OSGPU_EHD static cfloat f(cfloat a, cfloat b) { return cmul<cfloat, float>(a, b); }
 };
 
+// 16-bit floating point (extension types) ----------------------------------
+// An element is a 16-bit pattern: IEEE-754 binary16 (half_t) or bfloat16
+// (bf16_t, 1-8-7).  Two distinct class types, not int16_t: the op set and
+// the fold order are picked by type (kernel_common.hpp dispatch_op).
+//  * sum / prod: the correctly rounded (RNE) result in the element's own
+//    format, subnormals kept, overflow to +-inf.  Defined as: widen both
+//    operands to float (exact), ONE float operation, narrow RNE -- the double
+//    rounding is innocuous because float's 24 significand bits are at least
+//    2 * 11 + 2 and 2 * 8 + 2.  The host takes that route with an integer
+//    narrowing; the device takes v_add_f16 / v_mul_f16 (v_pk_* when the
+//    compiler pairs them) for half_t, which is the same function, and f32
+//    arithmetic + v_cvt_pk_bf16_f32 for bf16_t;
+//  * NaN results: the SSE rule at the element's width -- the first operand's
+//    NaN quieted (| 0x0200 / | 0x0040, payload and sign kept), else the
+//    second's, else (inf - inf, 0 * inf) the negative default NaN 0xFE00 /
+//    0xFFC0;
+//  * max / min: compare on the values, select the chosen operand's 16 bits.
+struct half_t { uint16_t u; };
+struct bf16_t { uint16_t u; };
+
+template <typename T> struct is_f16 { static constexpr bool value = false; };
+template <> struct is_f16<half_t> { static constexpr bool value = true; };
+template <> struct is_f16<bf16_t> { static constexpr bool value = true; };
+
+OSGPU_EHD bool isnan_(half_t x) { return (x.u & 0x7fffu) > 0x7c00u; }
+OSGPU_EHD bool isnan_(bf16_t x) { return (x.u & 0x7fffu) > 0x7f80u; }
+OSGPU_EHD half_t quiet(half_t x) { return half_t{(uint16_t) (x.u | 0x0200u)}; }
+OSGPU_EHD bf16_t quiet(bf16_t x) { return bf16_t{(uint16_t) (x.u | 0x0040u)}; }
+OSGPU_EHD half_t defnan(half_t) { return half_t{0xfe00u}; }
+OSGPU_EHD bf16_t defnan(bf16_t) { return bf16_t{0xffc0u}; }
+
+// exact widening (every binary16 / bfloat16 value is a float)
+OSGPU_EHD float widen(bf16_t x) { return flt((uint32_t) x.u << 16); }
+OSGPU_EHD float widen(half_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float) __builtin_bit_cast(_Float16, x.u);
+#else
+    const uint32_t s = (uint32_t) (x.u & 0x8000u) << 16, e = (x.u >> 10) & 0x1fu, m = x.u & 0x3ffu;
+    if (e == 0) return flt(s | bits((float) m * 0x1p-24f));  // zero / subnormal: m * 2^-24
+    if (e == 31) return flt(s | 0x7f800000u | (m << 13));
+    return flt(s | ((e + 112u) << 23) | (m << 13));
+#endif
+}
+
+// RNE narrowing of a float; a NaN narrows to some NaN (callers replace it)
+OSGPU_EHD bf16_t narrow(float r, bf16_t)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return bf16_t{__builtin_bit_cast(uint16_t, (__bf16) r)};  // v_cvt_pk_bf16_f32
+#else
+    const uint32_t x = bits(r);
+    if ((x << 1) > (0x7f800000u << 1)) return bf16_t{(uint16_t) ((x >> 16) | 0x0040u)};
+    return bf16_t{(uint16_t) ((x + 0x7fffu + ((x >> 16) & 1u)) >> 16)};
+#endif
+}
+OSGPU_EHD half_t narrow(float r, half_t)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return half_t{__builtin_bit_cast(uint16_t, (_Float16) r)};
+#else
+    const uint32_t x = bits(r) & 0x7fffffffu, s = (bits(r) >> 16) & 0x8000u;
+    uint32_t o;
+    if (x > 0x7f800000u) o = 0x7e00u;
+    else if (x >= 0x47800000u) o = 0x7c00u;  // 2^16 and above, inf
+    else if (x < 0x38800000u)                // below 2^-14: a multiple of 2^-24, by the
+        o = bits(flt(x) + 0.5f) - 0x3f000000u;  // float adder's own RNE at 0.5's ulp
+    else {
+        const uint32_t y = x - 0x38000000u;  // exponent rebias; a carry out of the
+        o = (y + 0xfffu + ((y >> 13) & 1u)) >> 13;  // significand steps the exponent (to inf)
+    }
+    return half_t{(uint16_t) (s | o)};
+#endif
+}
+
+// a OP b rounded once to the element's format; a NaN result is SOME NaN
+template <typename H, int OP>
+OSGPU_EHD H arith16(H a, H b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (__is_same(H, half_t)) {
+        const _Float16 x = __builtin_bit_cast(_Float16, a.u), y = __builtin_bit_cast(_Float16, b.u);
+        return half_t{__builtin_bit_cast(uint16_t, (_Float16) (OP == OP_SUM ? x + y : x * y))};
+    }
+#endif
+    const float x = widen(a), y = widen(b);
+    return narrow(OP == OP_SUM ? x + y : x * y, H{});
+}
+OSGPU_EHD bool gt16(bf16_t a, bf16_t b) { return widen(a) > widen(b); }
+OSGPU_EHD bool lt16(bf16_t a, bf16_t b) { return widen(a) < widen(b); }
+#if defined(__HIP_DEVICE_COMPILE__)
+OSGPU_EHD bool gt16(half_t a, half_t b)
+{
+    return __builtin_bit_cast(_Float16, a.u) > __builtin_bit_cast(_Float16, b.u);
+}
+OSGPU_EHD bool lt16(half_t a, half_t b)
+{
+    return __builtin_bit_cast(_Float16, a.u) < __builtin_bit_cast(_Float16, b.u);
+}
+#else
+OSGPU_EHD bool gt16(half_t a, half_t b) { return widen(a) > widen(b); }
+OSGPU_EHD bool lt16(half_t a, half_t b) { return widen(a) < widen(b); }
+#endif
+
+template <typename H, int OP> struct Elem16 {
+    OSGPU_EHD static H f(H a, H b)
+    {
+        if (OP == OP_MAX) return gt16(a, b) ? a : b;
+        if (OP == OP_MIN) return lt16(a, b) ? a : b;
+        H r = arith16<H, OP>(a, b);
+        if (__builtin_expect(isnan_(r), 0))
+            r = isnan_(a) ? quiet(a) : (isnan_(b) ? quiet(b) : defnan(a));
+        return r;
+    }
+};
+template <> struct Elem<half_t, OP_SUM> : Elem16<half_t, OP_SUM> {};
+template <> struct Elem<half_t, OP_PROD> : Elem16<half_t, OP_PROD> {};
+template <> struct Elem<half_t, OP_MAX> : Elem16<half_t, OP_MAX> {};
+template <> struct Elem<half_t, OP_MIN> : Elem16<half_t, OP_MIN> {};
+template <> struct Elem<bf16_t, OP_SUM> : Elem16<bf16_t, OP_SUM> {};
+template <> struct Elem<bf16_t, OP_PROD> : Elem16<bf16_t, OP_PROD> {};
+template <> struct Elem<bf16_t, OP_MAX> : Elem16<bf16_t, OP_MAX> {};
+template <> struct Elem<bf16_t, OP_MIN> : Elem16<bf16_t, OP_MIN> {};
+
 // ------------------------------------------------------- branch-free folds
 // Fast<T, OP>::f is Elem<T, OP>::f without its NaN handling (the SSE rule,
 // the complex product's libgcc recovery): one instruction stream with no
@@ -224,6 +348,15 @@ template <> struct Fast<float, OP_SUM> : FastReal<float, OP_SUM> {};
 template <> struct Fast<float, OP_PROD> : FastReal<float, OP_PROD> {};
 template <> struct Fast<double, OP_SUM> : FastReal<double, OP_SUM> {};
 template <> struct Fast<double, OP_PROD> : FastReal<double, OP_PROD> {};
+template <typename H, int OP> struct Fast16 {
+    static constexpr bool kChecked = true;
+    OSGPU_EHD static H f(H a, H b) { return arith16<H, OP>(a, b); }
+    OSGPU_EHD static bool bad(H r) { return isnan_(r); }
+};
+template <> struct Fast<half_t, OP_SUM> : Fast16<half_t, OP_SUM> {};
+template <> struct Fast<half_t, OP_PROD> : Fast16<half_t, OP_PROD> {};
+template <> struct Fast<bf16_t, OP_SUM> : Fast16<bf16_t, OP_SUM> {};
+template <> struct Fast<bf16_t, OP_PROD> : Fast16<bf16_t, OP_PROD> {};
 template <> struct Fast<cdouble, OP_SUM> {
     static constexpr bool kChecked = true;
     OSGPU_EHD static cdouble f(cdouble a, cdouble b)

@@ -38,12 +38,13 @@ template <int OP>
 using op_tag = std::integral_constant<int, OP>;
 
 // f(type_tag<T>, op_tag<OP>) for the ops T admits -- integers all seven,
-// real types sum / prod / max / min, complex types sum / prod -- else fallback
+// real types (half_t and bf16_t among them) sum / prod / max / min, complex
+// types sum / prod -- else fallback
 template <typename T, typename R, typename F>
 R dispatch_op(int op, R fallback, F &&f)
 {
     constexpr bool kInt = std::is_integral<T>::value;
-    constexpr bool kOrdered = kInt || std::is_floating_point<T>::value;
+    constexpr bool kOrdered = kInt || std::is_floating_point<T>::value || is_f16<T>::value;
     switch (op) {
     case OP_SUM: return f(type_tag<T>{}, op_tag<OP_SUM>{});
     case OP_PROD: return f(type_tag<T>{}, op_tag<OP_PROD>{});
@@ -71,6 +72,8 @@ R dispatch_type_op(int type, int op, R fallback, F &&f)
     case T_DOUBLE: return dispatch_op<double>(op, fallback, f);
     case T_COMPLEXF: return dispatch_op<cfloat>(op, fallback, f);
     case T_COMPLEXD: return dispatch_op<cdouble>(op, fallback, f);
+    case T_HALF: return dispatch_op<half_t>(op, fallback, f);
+    case T_BFLOAT16: return dispatch_op<bf16_t>(op, fallback, f);
     }
     return fallback;
 }

@@ -297,6 +297,7 @@ size_t type_size(int t)
     case OSGPU_T_LONGDOUBLE: return sizeof(long double);
     case OSGPU_T_COMPLEXF: return 2 * sizeof(float);
     case OSGPU_T_COMPLEXD: return 2 * sizeof(double);
+    case OSGPU_T_HALF: case OSGPU_T_BFLOAT16: return 2;
     }
     return 0;
 }
@@ -310,6 +311,12 @@ bool has_op(int t, int op)
     case OSGPU_OP_MAX: case OSGPU_OP_MIN: return t <= OSGPU_T_LONGDOUBLE;
     }
     return false;
+}
+
+bool has_ext_op(int t, int op)
+{
+    if (t != OSGPU_T_HALF && t != OSGPU_T_BFLOAT16) return false;
+    return op == OSGPU_OP_SUM || op == OSGPU_OP_PROD || op == OSGPU_OP_MAX || op == OSGPU_OP_MIN;
 }
 
 // ------------------------------------------------------------- PE services
@@ -1525,7 +1532,7 @@ void *osgpu_get_stream(void)
 int osgpu_combine(int type, int op, void *target, const void *const *srcs, int nsrc,
                   size_t nelems, void *hip_stream)
 {
-    if (!has_op(type, op) || nsrc < 1 || !target || !srcs) {
+    if (!(has_op(type, op) || has_ext_op(type, op)) || nsrc < 1 || !target || !srcs) {
         set_err("osgpu_combine: bad arguments");
         return OSGPU_EINVAL;
     }
@@ -1551,7 +1558,8 @@ int osgpu_team_combine(int type, int op, int P, void *const *dsts, const void *c
 int osgpu_team_combine_shape(int type, int op, int P, void *const *dsts, const void *const *srcs,
                              size_t nelems, void *hip_stream, int remote)
 {
-    if (!has_op(type, op) || P < 2 || P > osgpu::kMaxTeam || !dsts || !srcs) {
+    if (!(has_op(type, op) || has_ext_op(type, op)) || P < 2 || P > osgpu::kMaxTeam || !dsts ||
+        !srcs) {
         set_err("osgpu_team_combine: bad arguments");
         return OSGPU_EINVAL;
     }
@@ -1711,6 +1719,8 @@ int osgpu_compare(const void *a, const void *b, size_t nbytes, void *hip_stream,
 }
 
 int osgpu_has_op(int type, int op) { return has_op(type, op) ? 1 : 0; }
+
+int osgpu_has_ext_op(int type, int op) { return has_ext_op(type, op) ? 1 : 0; }
 
 size_t osgpu_type_size(int type) { return type_size(type); }
 

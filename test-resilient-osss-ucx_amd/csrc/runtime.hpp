@@ -59,6 +59,8 @@ void call_trace(int me, int phase, const char *label);
 
 size_t type_size(int t);
 bool has_op(int t, int op);
+// the extension types' table (half, bfloat16: sum / prod / max / min)
+bool has_ext_op(int t, int op);
 
 // ------------------------------------------------------------- PE services
 

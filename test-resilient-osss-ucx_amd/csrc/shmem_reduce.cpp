@@ -438,6 +438,8 @@ void run_fused(const Call &c, SyncSet &S, const std::vector<const void *> &srcs,
 //    every PE, where the reference folds in a per-PE order
 //    (src/reductions.c:79-111): within tolerance only, so only when the
 //    caller forces OSGPU_PATH_RCCL (`fp_ok`);
+//  * half / bfloat16 (the extension types): never, for any op -- one
+//    rounding per step in the per-PE order is their definition;
 //  * FP min/max: never.  The reference's `a<b?a:b` / `a>b?a:b`
 //    (src/shmemu/miscops.c:80-90) resolves NaN and signed-zero ties by fold
 //    position; RCCL's min/max do not follow it.
@@ -791,7 +793,9 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
     // RCCL only where its result is the reference's: integer (type, op)s on
     // the automatic path when no device heap is registered; FP sum/prod only
     // when the caller forces OSGPU_PATH_RCCL (tolerance, not bit-exact); FP
-    // min/max never (they take the exact kernels even when RCCL is forced).
+    // min/max never (they take the exact kernels even when RCCL is forced),
+    // and the extension types (half, bfloat16) never: rccl_types has no row
+    // for them, so they run the exact kernels under every setting.
     if (mode == OSGPU_PATH_RCCL && rccl_usable(c, true)) {
         run_rccl(c);
     } else if (mode != OSGPU_PATH_PULL && (idx = team_ptrs(c, srcs, dsts, &remote)) >= 0) {
@@ -880,3 +884,40 @@ OSGPU_DEFINE_MINMAX(longlong, long long, OSGPU_T_LONGLONG)
 OSGPU_DEFINE_MINMAX(float, float, OSGPU_T_FLOAT)
 OSGPU_DEFINE_MINMAX(double, double, OSGPU_T_DOUBLE)
 OSGPU_DEFINE_MINMAX(longdouble, long double, OSGPU_T_LONGDOUBLE)
+
+// ======================================================================
+// Part 1c: extension types (half, bfloat16).  Elements are 16-bit patterns;
+// the same funnel as Part 1, so every path and setting applies.
+// ======================================================================
+
+#define OSGPU_DEFINE_EXT(_name, _op, _tcode, _ocode)                           \
+    extern "C" void osgpu_##_name##_##_op##_reduce(                            \
+        uint16_t *target, const uint16_t *source, int nreduce, int PE_start,   \
+        int logPE_stride, int PE_size, uint16_t *pWrk, long *pSync)            \
+    {                                                                          \
+        to_all("osgpu_" #_name "_" #_op "_reduce", _tcode, _ocode, target,     \
+               const_cast<uint16_t *>(source), nreduce, PE_start,              \
+               logPE_stride, PE_size, pWrk, pSync);                            \
+    }
+
+#define OSGPU_DEFINE_EXT_OPS(_name, _tcode)                                    \
+    OSGPU_DEFINE_EXT(_name, sum, _tcode, OSGPU_OP_SUM)                         \
+    OSGPU_DEFINE_EXT(_name, prod, _tcode, OSGPU_OP_PROD)                       \
+    OSGPU_DEFINE_EXT(_name, max, _tcode, OSGPU_OP_MAX)                         \
+    OSGPU_DEFINE_EXT(_name, min, _tcode, OSGPU_OP_MIN)
+
+OSGPU_DEFINE_EXT_OPS(half, OSGPU_T_HALF)
+OSGPU_DEFINE_EXT_OPS(bfloat16, OSGPU_T_BFLOAT16)
+
+extern "C" void osgpu_reduce_ext(int type, int op, void *target, const void *source, int nreduce,
+                                 int PE_start, int logPE_stride, int PE_size, void *pWrk,
+                                 long *pSync)
+{
+    if (!osgpu::rt::has_ext_op(type, op))
+        osgpu::rt::fatal("osgpu_reduce_ext",
+                         "type %d op %d is not an extension reduction (half = %d, bfloat16 = "
+                         "%d; sum, prod, max, min)",
+                         type, op, (int) OSGPU_T_HALF, (int) OSGPU_T_BFLOAT16);
+    to_all("osgpu_reduce_ext", type, op, target, const_cast<void *>(source), nreduce, PE_start,
+           logPE_stride, PE_size, pWrk, pSync);
+}

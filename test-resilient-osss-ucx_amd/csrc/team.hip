@@ -120,10 +120,19 @@ struct TeamShape {
     // overall (cases 0.989-1.110x; r06_team_lds56_ab.jsonl); complex types
     // and FP max/min lost (0.72-0.98x, r06_team_lds_p58_ab.jsonl), and so
     // did every case at 7 members (7-wave workgroups, 0.78-0.99x).
-    static constexpr bool kFpMinMax = std::is_floating_point<T>::value && (OP == OP_MAX || OP == OP_MIN);
-    static constexpr bool kLds = REMOTE ? (P >= 3 && P <= 4)
-                                        : ((P >= OSGPU_TEAM_LDS_MIN_P && P <= OSGPU_TEAM_LDS_MAX_P) ||
-                                           ((P == 5 || P == 6 || P == 8) && !kComplex && !kFpMinMax));
+    static constexpr bool kFpMinMax = (std::is_floating_point<T>::value || is_f16<T>::value) &&
+                                      (OP == OP_MAX || OP == OP_MIN);
+    // half_t / bf16_t: the LDS form at every member count above 4 too, for
+    // every op, local and remote.  Eight elements per vector make the register
+    // form's P outputs of one lane too large there (bf16_t max at 8 members:
+    // 238 VGPRs, 2 waves per SIMD; sum at 7: the fold loop is not unrolled
+    // and its arrays go to scratch), while a wave of the LDS form folds one
+    // output.  The register form serves them at 2 remote members only.
+    static constexpr bool kLds = is_f16<T>::value
+                                     ? (REMOTE ? P >= 3 : P >= OSGPU_TEAM_LDS_MIN_P)
+                                 : REMOTE ? (P >= 3 && P <= 4)
+                                          : ((P >= OSGPU_TEAM_LDS_MIN_P && P <= OSGPU_TEAM_LDS_MAX_P) ||
+                                             ((P == 5 || P == 6 || P == 8) && !kComplex && !kFpMinMax));
     static constexpr int kLdsU = OSGPU_TEAM_LDS_U;
     // the rounds g = 0, G, 2G, ... must tile [0, U) exactly, or the last
     // round reads and writes past the tile (and past nvec)

@@ -23,6 +23,19 @@ HEADER = os.path.join(REPO, "include", "osgpu_reduce.h")
 TYPES = ["short", "int", "long", "longlong", "float", "double",
          "longdouble", "complexf", "complexd"]
 OPS = ["sum", "prod", "and", "or", "xor", "max", "min"]
+# extension types (include/osgpu_reduce.h Part 1c): elements are 16-bit
+# patterns (uint16), type codes 9 and 10, ops sum / prod / max / min
+EXT_TYPES = ["half", "bfloat16"]
+EXT_OPS = ["sum", "prod", "max", "min"]
+
+
+def type_code(name: str) -> int:
+    """The osgpu_type code of a type of TYPES or EXT_TYPES."""
+    if name in EXT_TYPES:
+        return len(TYPES) + EXT_TYPES.index(name)
+    return TYPES.index(name)
+
+
 CTYPE = {
     "short": ctypes.c_short, "int": ctypes.c_int, "long": ctypes.c_long,
     "longlong": ctypes.c_longlong, "float": ctypes.c_float,
@@ -146,6 +159,14 @@ def load() -> ctypes.CDLL:
     L.osgpu_team_combine_shape.argtypes = [i, i, i, vp, vp, sz, vp, i]
     L.osgpu_build_id.restype = ctypes.c_char_p
     L.osgpu_has_op.argtypes = [i, i]
+    L.osgpu_has_ext_op.argtypes = [i, i]
+    for t in EXT_TYPES:
+        for o in EXT_OPS:
+            f = getattr(L, f"osgpu_{t}_{o}_reduce")
+            f.argtypes = [vp, vp, i, i, i, i, vp, vp]
+            f.restype = None
+    L.osgpu_reduce_ext.argtypes = [i, i, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_reduce_ext.restype = None
     L.osgpu_type_size.argtypes = [i]
     L.osgpu_type_size.restype = sz
     L.osgpu_fold_order.argtypes = [i, i, i, i, ctypes.POINTER(ctypes.c_int)]
@@ -201,7 +222,7 @@ class host_path:
 def checksum(t: str, mode: int, ptr: int, n: int, stream: int | None = None) -> int:
     """osgpu_checksum over n elements of type t at device address ptr."""
     out = ctypes.c_ulonglong()
-    rc = load().osgpu_checksum(TYPES.index(t), mode, ptr, n, stream, ctypes.byref(out))
+    rc = load().osgpu_checksum(type_code(t), mode, ptr, n, stream, ctypes.byref(out))
     if rc != 0:
         raise RuntimeError(load().osgpu_last_error().decode())
     return out.value
@@ -307,11 +328,29 @@ def to_all(t: str, op: str):
     return getattr(load(), f"shmem_{t}_{op}_to_all")
 
 
+def ext_reduce(t: str, op: str):
+    """The ctypes function osgpu_<t>_<op>_reduce (t of EXT_TYPES)."""
+    return getattr(load(), f"osgpu_{t}_{op}_reduce")
+
+
+def team_combine(t: str, op: str, dsts, srcs, n: int, stream: int | None = None,
+                 remote: bool = False):
+    """Enqueue the owner-computes team kernel: dsts[q] = fold of srcs in member
+    q's order (device ptrs); remote: the shapes of a call across GPUs."""
+    L = load()
+    P = len(srcs)
+    rc = L.osgpu_team_combine_shape(type_code(t), OPS.index(op), P, (ctypes.c_void_p * P)(*dsts),
+                                    (ctypes.c_void_p * P)(*srcs), n, stream, int(remote))
+    if rc != 0:
+        raise RuntimeError(f"osgpu_team_combine({t},{op}) = {rc}: "
+                           f"{L.osgpu_last_error().decode()}")
+
+
 def combine(t: str, op: str, target: int, srcs, n: int, stream: int | None = None):
     """Enqueue the combine kernel: target = fold(op, srcs...) (device ptrs)."""
     L = load()
     arr = (ctypes.c_void_p * len(srcs))(*srcs)
-    rc = L.osgpu_combine(TYPES.index(t), OPS.index(op), target, arr, len(srcs), n,
+    rc = L.osgpu_combine(type_code(t), OPS.index(op), target, arr, len(srcs), n,
                          stream)
     if rc != 0:
         raise RuntimeError(f"osgpu_combine({t},{op}) = {rc}: "
