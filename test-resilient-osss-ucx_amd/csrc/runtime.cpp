@@ -539,12 +539,13 @@ MemKind mem_kind(const void *p, int *dev)
     return MEM_HOST;
 }
 
-bool ranges_overlap(const void *a, const void *b, size_t n)
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
     // byte-exact: the reference's OVERLAP_CHECK (src/reductions.c:27-30)
     // adds a byte count to a typed pointer and over-detects by sizeof(T)
-    uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-    return (x < y + n) && (y < x + n);
+    if (!na || !nb) return false;
+    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
+    return x < y + nb && y < x + na;
 }
 
 void fold_order(int me, int PE_start, int step, int PE_size, int *order)

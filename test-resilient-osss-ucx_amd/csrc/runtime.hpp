@@ -3,6 +3,7 @@
 // OpenSHMEM PE services the library borrows from the application's runtime,
 // the device symmetric-heap registry, per-PE streams/scratch, the RCCL
 // communicator, and the host-staging sets of the STAGED paths.
+// The per-call helpers built on these services are call_common.hpp.
 // Not installed: the public surface is include/osgpu_reduce.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -110,7 +111,8 @@ void *host_stage(const char *where, int me, size_t bytes);
 
 enum MemKind { MEM_HOST = 0, MEM_DEVICE = 1 };
 MemKind mem_kind(const void *p, int *dev);
-bool ranges_overlap(const void *a, const void *b, size_t n);
+// do [a, a + na) and [b, b + nb) share a byte?  (false when either is empty)
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
 void fold_order(int me, int PE_start, int step, int PE_size, int *order);
 
 // ------------------------------------------------------------ active sets

@@ -66,6 +66,7 @@
 // src/shmemc/barrier.c:64-97), reads its peers' with shmem_getmem after the
 // first barrier and clears its word after the last -- pSync is returned at
 // SHMEM_SYNC_VALUE, as the reference's wavefront leaves it (collect.c:67).
+// The per-call scaffolding shared with shmem_reduce.cpp is call_common.hpp.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -76,6 +77,7 @@
 #include <vector>
 
 #include "../../include/osgpu_reduce.h"
+#include "call_common.hpp"
 #include "combine.hpp"
 #include "runtime.hpp"
 
@@ -111,13 +113,6 @@ struct CCall : Coll {
     std::vector<Piece> pieces;     // what my target receives
     size_t out_bytes = 0;          // extent of my target that is written (alltoalls: spanned)
 };
-
-bool overlap2(const void *a, size_t na, const void *b, size_t nb)
-{
-    if (!na || !nb) return false;
-    const uintptr_t x = (uintptr_t) a, y = (uintptr_t) b;
-    return x < y + nb && y < x + na;
-}
 
 // Every member's nelems (collect), through pSync[kCountWord] + getmem.
 void exchange_counts(CCall &c)
@@ -191,11 +186,9 @@ bool my_source_read(const CCall &c)
 
 void copy_pieces(const CCall &c, const std::vector<osgpu::CopySeg> &segs, hipStream_t st)
 {
-    for (size_t i = 0; i < segs.size(); i += osgpu::kMaxCopySegs) {
-        const int n = (int) std::min(segs.size() - i, (size_t) osgpu::kMaxCopySegs);
-        hipError_t e = osgpu::launch_copy(segs.data() + i, n, st);
-        if (e != hipSuccess) fatal(c.name, "copy launch: %s", hipGetErrorString(e));
-    }
+    for_batches(segs, osgpu::kMaxCopySegs, [&](const osgpu::CopySeg *b, int n) {
+        launched(c.name, "copy launch", osgpu::launch_copy(b, n, st));
+    });
 }
 
 // ------------------------------------------------------------ COPY (device)
@@ -247,36 +240,22 @@ bool fused_copy_eligible(const CCall &c)
 }
 
 void run_fused_copy(const CCall &c, SyncSet &S, const std::vector<osgpu::CopySeg> &segs,
-                    char *out, hipStream_t st)
+                    const DeviceOut &out, hipStream_t st)
 {
-    osgpu::FusedArgs a;
-    memset(&a, 0, sizeof(a));
+    osgpu::FusedArgs a = fused_args(c, S);
     a.nseg = (int) segs.size();
     for (int d = 0; d < a.nseg; d++) {
         a.src[d] = segs[d].src;
         a.dst[d] = segs[d].dst;
         a.seg_bytes[d] = segs[d].bytes;
     }
-    for (int i = 0; i < c.PE_size; i++) a.flags[i] = S.peer[i];
-    a.mine = S.local;
-    a.err = S.err_d;
-    a.done_host = S.done_d;
-    a.epoch = ++S.epoch;
-    a.P = c.PE_size;
-    a.me = S.idx;
-    a.max_blocks = S.max_blocks;
     DBG("%s PE %d: fused copy, %d pieces, epoch %llu", c.name, c.me, a.nseg, a.epoch);
-    entry_order(c.name, st);
-    if (!fused_complete(c.name, S, st, a,
-                        [&](const osgpu::FusedArgs &x) { return osgpu::launch_fused_copy(x, st); })) {
+    if (!fused_run(c, S, st, a,
+                   [&](const osgpu::FusedArgs &x) { return osgpu::launch_fused_copy(x, st); })) {
         t_last_coll = OSGPU_RAN_FUSED_FAILED;
         return;
     }
-    if (out != (char *) c.target) {  // every reader of my source is done: exit barrier passed
-        if (c.out_bytes)
-            HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.out_bytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.out_bytes, st);  // every reader of my source is done: exit barrier passed
 }
 
 // Host heaps pinned on every PE (osgpu_host_register): a small broadcast /
@@ -300,8 +279,7 @@ bool run_fused_staged_copy(const CCall &c, StageSet &G)
     SyncSet *S = sync_setup(c);
     if (!S) return false;
     t_last_coll = OSGPU_RAN_FUSED_STAGED;
-    osgpu::FusedArgs a;
-    memset(&a, 0, sizeof(a));
+    osgpu::FusedArgs a = fused_args(c, *S);
     for (const Piece &p : c.pieces) {
         if (!p.len) continue;
         a.src[a.nseg] = G.region(p.from) + p.src_off;
@@ -312,19 +290,10 @@ bool run_fused_staged_copy(const CCall &c, StageSet &G)
     a.host_in = hin;
     a.stage_mine = G.region(c.idx);
     a.host_bytes = mine;
-    for (int i = 0; i < c.PE_size; i++) a.flags[i] = S->peer[i];
-    a.mine = S->local;
-    a.err = S->err_d;
-    a.done_host = S->done_d;
-    a.epoch = ++S->epoch;
-    a.P = c.PE_size;
-    a.me = S->idx;
-    a.max_blocks = S->max_blocks;
     DBG("%s PE %d: fused staged copy, %d pieces, epoch %llu", c.name, c.me, a.nseg, a.epoch);
     hipStream_t st = pe_stream(c.name, c.me);
-    entry_order(c.name, st);
-    if (!fused_complete(c.name, *S, st, a,
-                        [&](const osgpu::FusedArgs &x) { return osgpu::launch_fused_copy(x, st); }))
+    if (!fused_run(c, *S, st, a,
+                   [&](const osgpu::FusedArgs &x) { return osgpu::launch_fused_copy(x, st); }))
         t_last_coll = OSGPU_RAN_FUSED_FAILED;
     return true;
 }
@@ -337,8 +306,9 @@ bool run_fused_staged_copy(const CCall &c, StageSet &G)
 //   1  the launch exchanged the counts (c.src_len) and passed the entry
 //      barrier; the pieces are left to the COPY path (total over the limit);
 //   0  not eligible: the host exchanges the counts.
-int fused_collect(CCall &c)
+int fused_collect(CCall &c, int dev)
 {
+    const DeviceGuard on_device(c.name, dev);
     const int em = entry_mode();
     const size_t lim = fused_max_bytes();
     const int P = c.PE_size;
@@ -351,38 +321,29 @@ int fused_collect(CCall &c)
     int seg = -1;
     size_t off = 0;
     if (!heap_locate(c.me, c.source, mine ? mine : 1, &seg, &off)) return 0;
-    osgpu::FusedArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < P; i++) {
-        HeapEntry h;
-        if (!heap_segment(c.pe_at(i), seg, &h) || off >= h.bytes) return 0;
-        a.src[i] = h.base + off;
-        a.src_avail[i] = h.bytes - off;
-    }
+    HeapEntry heap[osgpu::kMaxTeam];  // P <= kMaxTeam
+    for (int i = 0; i < P; i++)
+        if (!heap_segment(c.pe_at(i), seg, &heap[i]) || off >= heap[i].bytes) return 0;
     SyncSet *S = sync_setup(c);
     if (!S) return 0;
     hipStream_t st = pe_stream(c.name, c.me);
     // my output: the target, or scratch when the target (at most `lim` bytes
     // if copied here) may overlap my source, which peers read in the launch
-    const bool scratch = overlap2(c.target, lim, c.source, mine);
-    char *out = scratch ? (char *) device_scratch(c.name, c.me, lim) : (char *) c.target;
-    for (int i = 0; i < P; i++) a.flags[i] = S->peer[i];
-    a.dst[0] = out;
-    a.mine = S->local;
-    a.err = S->err_d;
-    a.done_host = S->done_d;
-    a.counts_host = S->cnt_d;
-    a.epoch = ++S->epoch;
-    a.P = P;
-    a.me = S->idx;
-    a.max_blocks = S->max_blocks;
+    // (a scratch call has mine > 0, so it gathers a total > 0)
+    const DeviceOut out(c, c.target, ranges_overlap(c.target, lim, c.source, mine), lim);
     if (mine >> osgpu::kCountBits) fatal(c.name, "contribution of %zu bytes too large", mine);
+    osgpu::FusedArgs a = fused_args(c, *S);
+    for (int i = 0; i < P; i++) {
+        a.src[i] = heap[i].base + off;
+        a.src_avail[i] = heap[i].bytes - off;
+    }
+    a.dst[0] = out.out;
+    a.counts_host = S->cnt_d;
     a.my_count = mine;
     a.count_tag = ++S->ncollect;
     a.copy_limit = lim;
     DBG("%s PE %d: fused collect, %zu bytes mine, epoch %llu", c.name, c.me, mine, a.epoch);
-    entry_order(c.name, st);
-    if (!fused_complete(c.name, *S, st, a, [&](const osgpu::FusedArgs &x) {
+    if (!fused_run(c, *S, st, a, [&](const osgpu::FusedArgs &x) {
             return osgpu::launch_fused_collect(x, st);
         })) {
         t_last_coll = OSGPU_RAN_FUSED_FAILED;
@@ -393,10 +354,7 @@ int fused_collect(CCall &c)
     for (int i = 0; i < P; i++) total += (c.src_len[i] = (size_t) S->cnt_h[i]);
     if (!S->cnt_h[osgpu::kMaxTeam]) return 1;
     t_last_coll = OSGPU_RAN_FUSED_COPY;
-    if (scratch && total) {  // every reader of my source is done: the launch passed done
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, total, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(total, st);  // every reader of my source is done: the launch passed done
     return 2;
 }
 
@@ -404,11 +362,11 @@ void run_copy(const CCall &c, const std::vector<const char *> &src, bool counts_
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const bool scratch = my_source_read(c) &&
-                         overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
-    char *out = scratch ? (char *) device_scratch(c.name, c.me, c.out_bytes) : (char *) c.target;
+                         ranges_overlap(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
+    const DeviceOut out(c, c.target, scratch, c.out_bytes);
     std::vector<osgpu::CopySeg> segs;
     for (const Piece &p : c.pieces)
-        if (p.len) segs.push_back({src[p.from] + p.src_off, out + p.dst_off, p.len});
+        if (p.len) segs.push_back({src[p.from] + p.src_off, out.out + p.dst_off, p.len});
     SyncSet *Y = nullptr;
     if (!counts_done && fused_copy_eligible(c) && (Y = sync_setup(c))) {
         t_last_coll = OSGPU_RAN_FUSED_COPY;
@@ -425,10 +383,7 @@ void run_copy(const CCall &c, const std::vector<const char *> &src, bool counts_
     copy_pieces(c, segs, st);
     stream_wait(c.name, st);
     barrier(c);  // every reader of my source is done
-    if (scratch && c.out_bytes) {
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.out_bytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.out_bytes, st);
 }
 
 // alltoalls on device heaps: one StridedSeg per member through copy.hip's
@@ -440,8 +395,8 @@ void run_copy_strided(const CCall &c, const std::vector<const char *> &src)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t packed = (size_t) c.PE_size * c.nelems * c.esz;
-    const bool scratch = overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
-    char *out = scratch ? (char *) device_scratch(c.name, c.me, packed) : (char *) c.target;
+    const bool scratch = ranges_overlap(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
+    char *out = DeviceOut(c, c.target, scratch, packed).out;  // scattered below, not copied
     std::vector<osgpu::StridedSeg> segs;
     for (const Piece &p : c.pieces)
         segs.push_back({src[p.from] + p.src_off,
@@ -452,28 +407,21 @@ void run_copy_strided(const CCall &c, const std::vector<const char *> &src)
         c.me, segs.size(), c.nelems, c.dst, c.sst, scratch ? " (scratch)" : "");
     entry_sync(c.name);
     barrier(c);  // every source ready
-    for (size_t i = 0; i < segs.size(); i += osgpu::kMaxCopySegs) {
-        const int n = (int) std::min(segs.size() - i, (size_t) osgpu::kMaxCopySegs);
-        hipError_t e = osgpu::launch_strided_copy((int) c.esz, segs.data() + i, n, st);
-        if (e != hipSuccess) fatal(c.name, "strided copy launch: %s", hipGetErrorString(e));
-    }
+    for_batches(segs, osgpu::kMaxCopySegs, [&](const osgpu::StridedSeg *b, int n) {
+        launched(c.name, "strided copy launch",
+                 osgpu::launch_strided_copy((int) c.esz, b, n, st));
+    });
     stream_wait(c.name, st);
     barrier(c);  // every reader of my source is done
     if (scratch) {
         const osgpu::StridedSeg g = {out, c.target, (size_t) c.PE_size * c.nelems, 1, c.dst};
-        hipError_t e = osgpu::launch_strided_copy((int) c.esz, &g, 1, st);
-        if (e != hipSuccess) fatal(c.name, "strided copy launch: %s", hipGetErrorString(e));
+        launched(c.name, "strided copy launch",
+                 osgpu::launch_strided_copy((int) c.esz, &g, 1, st));
         stream_wait(c.name, st);
     }
 }
 
 // ------------------------------------------------------------ RCCL (device)
-
-bool rccl_whole_job(const CCall &c)
-{
-    return g_rccl.world && c.PE_start == 0 && c.step == 1 && c.PE_size == g_rccl.npes &&
-           c.me == g_rccl.me && (c.kind == K_BCAST || c.kind == K_FCOLLECT);
-}
 
 void run_rccl(const CCall &c)
 {
@@ -491,16 +439,13 @@ void run_rccl(const CCall &c)
         stream_wait(c.name, st);
         return;
     }
-    const bool scratch = overlap2(c.target, c.out_bytes, c.source, nb) &&
+    const bool scratch = ranges_overlap(c.target, c.out_bytes, c.source, nb) &&
                          (char *) c.target + (size_t) c.idx * nb != (const char *) c.source;
-    char *out = scratch ? (char *) device_scratch(c.name, c.me, c.out_bytes) : (char *) c.target;
-    r = ncclAllGather(c.source, out, nb, ncclUint8, g_rccl.world, st);
+    const DeviceOut out(c, c.target, scratch, c.out_bytes);
+    r = ncclAllGather(c.source, out.out, nb, ncclUint8, g_rccl.world, st);
     if (r != ncclSuccess) fatal(c.name, "ncclAllGather: %s", ncclGetErrorString(r));
     stream_wait(c.name, st);
-    if (scratch) {
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.out_bytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.out_bytes, st);
 }
 
 // ------------------------------------------------------------ STAGED (host)
@@ -522,9 +467,8 @@ void run_staged(const CCall &c, StageSet &S)
     for (size_t l : c.src_len) maxlen = std::max(maxlen, l);
     const size_t nchunks = (maxlen + C - 1) / C;
     const size_t mine = c.src_len[c.idx];
-    const bool tmp = overlap2(c.target, c.out_bytes, c.source, mine);
-    char *result = tmp ? (char *) malloc(c.out_bytes) : (char *) c.target;
-    if (tmp && !result) fatal(c.name, "out of memory for the temporary target");
+    HostTmp result(c, c.target, ranges_overlap(c.target, c.out_bytes, c.source, mine),
+                   c.out_bytes);
     char *in_me = S.region(c.idx);
     char *out_me = S.region(c.idx) + C;
     std::vector<osgpu::CopySeg> segs;
@@ -554,14 +498,11 @@ void run_staged(const CCall &c, StageSet &S)
         stream_wait(c.name, S.st_c);
         barrier(c);  // every reader of chunk k is done
         for (size_t i = 0; i < segs.size(); i++)
-            HIPCHK(c.name, hipMemcpyAsync(result + seg_dst[i], segs[i].dst, segs[i].bytes,
+            HIPCHK(c.name, hipMemcpyAsync(result.out + seg_dst[i], segs[i].dst, segs[i].bytes,
                                           hipMemcpyDeviceToHost, S.st_out));
         stream_wait(c.name, S.st_out);
     }
-    if (tmp) {
-        memcpy(c.target, result, c.out_bytes);
-        free(result);
-    }
+    result.finish(c.out_bytes);
 }
 
 // GETMEM: the reference's linear schedule over the runtime's getmem (used
@@ -570,22 +511,17 @@ void run_staged(const CCall &c, StageSet &S)
 void run_getmem(const CCall &c)
 {
     t_last_coll = OSGPU_RAN_GETMEM;
-    if (!c.ops.getmem) fatal(c.name, "host-memory arguments need shmem_getmem");
-    const bool tmp = overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]) &&
+    const bool tmp = ranges_overlap(c.target, c.out_bytes, c.source, c.src_len[c.idx]) &&
                      my_source_read(c);
-    char *result = tmp ? (char *) malloc(c.out_bytes) : (char *) c.target;
-    if (tmp && !result) fatal(c.name, "out of memory for the temporary target");
+    HostTmp result(c, c.target, tmp, c.out_bytes);
     for (const Piece &p : c.pieces) {
         if (!p.len) continue;
         const char *s = (const char *) c.source + p.src_off;
-        if (p.from == c.idx) memmove(result + p.dst_off, s, p.len);
-        else c.ops.getmem(result + p.dst_off, s, p.len, c.pe_at(p.from));
+        if (p.from == c.idx) memmove(result.out + p.dst_off, s, p.len);
+        else c.ops.getmem(result.out + p.dst_off, s, p.len, c.pe_at(p.from));
     }
     barrier(c);  // every reader of my source is done
-    if (tmp) {
-        memcpy(c.target, result, c.out_bytes);
-        free(result);
-    }
+    result.finish(c.out_bytes);
 }
 
 // cnt elements of esz (4 or 8) bytes, ss / ds elements apart
@@ -606,11 +542,10 @@ void host_strided_copy(size_t esz, void *d, ptrdiff_t ds, const void *s, ptrdiff
 void run_getmem_strided(const CCall &c)
 {
     t_last_coll = OSGPU_RAN_GETMEM;
-    if (!c.ops.getmem) fatal(c.name, "host-memory arguments need shmem_getmem");
     const size_t total = (size_t) c.PE_size * c.nelems;
-    const bool tmp = overlap2(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
-    char *result = tmp ? (char *) malloc(total * c.esz) : (char *) c.target;
-    if (tmp && !result) fatal(c.name, "out of memory for the temporary target");
+    const bool tmp = ranges_overlap(c.target, c.out_bytes, c.source, c.src_len[c.idx]);
+    const HostTmp packed(c, c.target, tmp, total * c.esz);  // scattered below, freed at return
+    char *result = packed.out;
     const ptrdiff_t rst = tmp ? 1 : c.dst;
     const size_t pitch = (size_t) c.sst * c.esz;  // bytes from one source element to the next
     const size_t per = std::max<size_t>(host_chunk_bytes() / pitch, 1);  // elements per getmem
@@ -630,10 +565,7 @@ void run_getmem_strided(const CCall &c)
         }
     }
     barrier(c);  // every reader of my source is done
-    if (tmp) {
-        host_strided_copy(c.esz, c.target, c.dst, result, 1, total);
-        free(result);
-    }
+    if (tmp) host_strided_copy(c.esz, c.target, c.dst, result, 1, total);
 }
 
 // ------------------------------------------------------------ dispatcher
@@ -662,8 +594,7 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
         fatal(name, "PE_root %d outside the active set of %d PEs", PE_root, PE_size);
     if (kind != K_COLLECT && nelems == 0) {  // nothing moves; the collective still syncs
         t_last_coll = OSGPU_RAN_BARRIER_ONLY;
-        barrier(c);
-        barrier(c);
+        sync_only(c);
         return;
     }
     int dt = -1, ds = -1;
@@ -672,11 +603,7 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
 
     bool counts_done = false, psync_counts = false;
     if (kind == K_COLLECT && kt == MEM_DEVICE) {  // counts on the device arrival
-        int cur = 0;
-        HIPCHK(name, hipGetDevice(&cur));
-        if (cur != dt) HIPCHK(name, hipSetDevice(dt));
-        const int f = fused_collect(c);
-        if (cur != dt) HIPCHK(name, hipSetDevice(cur));
+        const int f = fused_collect(c, dt);
         if (f == 2) return;
         counts_done = f == 1;
     }
@@ -696,10 +623,7 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
     }
 
     if (kt == MEM_HOST) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            fatal(name, "no GPU visible: the collectives run on the GPU");
-        if (!c.ops.getmem) fatal(name, "host-memory arguments need shmem_getmem");
+        require_host_heaps(c);
         // STAGED moves 1 + P (in + out) bytes per target byte over each
         // PE's PCIe link; that beats the runtime's memcpy only for large
         // calls and only when every member has a GPU (and a link) of its
@@ -734,9 +658,7 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
         return;
     }
 
-    int cur = 0;
-    HIPCHK(name, hipGetDevice(&cur));
-    if (cur != dt) HIPCHK(name, hipSetDevice(dt));
+    const DeviceGuard on_device(name, dt);
     const int mode = path_mode();
     std::vector<const char *> src;
     if (kind == K_ALLTOALLS) {  // COPY only: no FUSED or RCCL form
@@ -747,7 +669,7 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
     } else if (mode != OSGPU_PATH_RCCL && device_sources(c, src)) {
         run_copy(c, src, counts_done);
     } else if ((mode == OSGPU_PATH_AUTO || mode == OSGPU_PATH_RCCL) && !counts_done &&
-               rccl_whole_job(c)) {
+               rccl_whole_job(c) && (kind == K_BCAST || kind == K_FCOLLECT)) {
         run_rccl(c);
     } else {
         fatal(name,
@@ -758,7 +680,6 @@ void collective(const char *name, Kind kind, size_t esz, void *target, const voi
                   : "");
     }
     if (psync_counts) c.pSync[kCountWord] = 0;
-    if (cur != dt) HIPCHK(name, hipSetDevice(cur));
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 //
 // The two shmem_barrier calls of the reference (:82, :113) keep their roles
 // (every source ready / every reader or writer done) on every non-RCCL path.
+// The per-call scaffolding shared with shmem_collect.cpp is call_common.hpp.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "../../include/osgpu_reduce.h"
+#include "call_common.hpp"
 #include "combine.hpp"
 #include "runtime.hpp"
 
@@ -56,23 +58,7 @@ struct Call : Coll {
     size_t nbytes = 0;
 };
 
-bool p2p_sources(const Call &c, std::vector<const void *> &srcs)
-{
-    int seg = -1;
-    size_t off = 0;
-    if (!heap_locate(c.me, c.source, c.nbytes, &seg, &off)) return false;
-    std::vector<int> order(c.PE_size);
-    fold_order(c.me, c.PE_start, c.step, c.PE_size, order.data());
-    srcs.resize(c.PE_size);
-    for (int k = 0; k < c.PE_size; k++) {
-        char *p = nullptr;
-        if (!heap_peer(order[k], seg, off, c.nbytes, &p)) return false;
-        srcs[k] = p;
-    }
-    return true;
-}
-
-// every member's source in active-set order (the fused pull form)
+// every member's source in active-set order (both pull forms)
 bool member_sources(const Call &c, std::vector<const void *> &srcs)
 {
     int seg = -1;
@@ -95,7 +81,7 @@ int team_ptrs(const Call &c, std::vector<const void *> &srcs, std::vector<void *
               bool *remote = nullptr)
 {
     if (c.PE_size < 2 || c.PE_size > osgpu::kMaxTeam) return -1;
-    if (ranges_overlap(c.target, c.source, c.nbytes)) return -1;
+    if (ranges_overlap(c.target, c.nbytes, c.source, c.nbytes)) return -1;
     int ss = -1, st = -1;
     size_t os = 0, ot = 0;
     if (!heap_locate(c.me, c.source, c.nbytes, &ss, &os)) return -1;
@@ -162,7 +148,6 @@ void run_team(const Call &c, const std::vector<const void *> &srcs,
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
-    const int es = (int) (s > 16 ? 16 : s);
     const int mode = local_mode();
     // (long double: contiguous shards or merged runs, no tiles)
     const bool tiles = mode == LOCAL_MERGE || (mode == LOCAL_TILES && c.type != osgpu::T_LONGDOUBLE);
@@ -196,8 +181,8 @@ void run_team(const Call &c, const std::vector<const void *> &srcs,
         while (last + 1 < c.PE_size && (mask >> (last + 1) & 1u)) last++;
     }
     long long lo = 0, hi = 0, t = 0;
-    osgpu_shard_range(c.nreduce, c.PE_size, first, es, &lo, &t);
-    osgpu_shard_range(c.nreduce, c.PE_size, last, es, &t, &hi);
+    shard_of(c.nreduce, c.PE_size, first, s, &lo, &t);
+    shard_of(c.nreduce, c.PE_size, last, s, &t, &hi);
     std::vector<const void *> sp(c.PE_size);
     std::vector<void *> dp(c.PE_size);
     for (int i = 0; i < c.PE_size; i++) {
@@ -212,11 +197,10 @@ void run_team(const Call &c, const std::vector<const void *> &srcs,
         m = 1;
         k = 0;
     }
-    if (hi > lo) {
-        hipError_t e = osgpu::launch_team_tiles(c.type, c.op, c.PE_size, dp.data(), sp.data(),
-                                                (size_t) (hi - lo), m, k, st, remote);
-        if (e != hipSuccess) fatal(c.name, "team combine launch: %s", hipGetErrorString(e));
-    }
+    if (hi > lo)
+        launched(c.name, "team combine launch",
+                 osgpu::launch_team_tiles(c.type, c.op, c.PE_size, dp.data(), sp.data(),
+                                          (size_t) (hi - lo), m, k, st, remote));
     call_trace(c.me, 3, "launch");
     DBG("%s PE %d: team kernel launched", c.name, c.me);
     stream_wait(c.name, st);
@@ -255,7 +239,7 @@ void run_team_push(const Call &c, const std::vector<const void *> &srcs,
     std::vector<long long> lo(P), hi(P);
     long long most = 0;
     for (int g = 0; g < P; g++) {
-        osgpu_shard_range(c.nreduce, P, g, (int) (s > 16 ? 16 : s), &lo[g], &hi[g]);
+        shard_of(c.nreduce, P, g, s, &lo[g], &hi[g]);
         most = std::max(most, hi[g] - lo[g]);
     }
     long long C = (long long) ((4 * S.slot) / (size_t) P / s) / g16 * g16;  // elements per slot
@@ -280,11 +264,9 @@ void run_team_push(const Call &c, const std::vector<const void *> &srcs,
                 segs.push_back({(const char *) srcs[idx] + (size_t) a * s,
                                 S.region(g) + (size_t) idx * C * s, (size_t) (b - a) * s});
         }
-        for (size_t i = 0; i < segs.size(); i += osgpu::kMaxCopySegs) {
-            const int m = (int) std::min(segs.size() - i, (size_t) osgpu::kMaxCopySegs);
-            hipError_t e = osgpu::launch_copy(segs.data() + i, m, st);
-            if (e != hipSuccess) fatal(c.name, "scatter launch: %s", hipGetErrorString(e));
-        }
+        for_batches(segs, osgpu::kMaxCopySegs, [&](const osgpu::CopySeg *b, int m) {
+            launched(c.name, "scatter launch", osgpu::launch_copy(b, m, st));
+        });
         stream_wait(c.name, st);
         barrier(c);  // every inbox holds chunk k; every member has entered (:82)
         const long long a = lo[idx] + k * C, b = std::min(hi[idx], a + C);
@@ -293,33 +275,35 @@ void run_team_push(const Call &c, const std::vector<const void *> &srcs,
                 sp[i] = S.region(idx) + (size_t) i * C * s;
                 dp[i] = (char *) dsts[i] + (size_t) a * s;
             }
-            hipError_t e = osgpu::launch_team(c.type, c.op, P, dp.data(), sp.data(),
-                                              (size_t) (b - a), st, S.ndev > 1);
-            if (e != hipSuccess) fatal(c.name, "team fold launch: %s", hipGetErrorString(e));
+            launched(c.name, "team fold launch",
+                     osgpu::launch_team(c.type, c.op, P, dp.data(), sp.data(), (size_t) (b - a),
+                                        st, S.ndev > 1));
             stream_wait(c.name, st);
         }
         barrier(c);  // inboxes drained; after the last chunk every target is complete (:113)
     }
 }
 
-void run_p2p(const Call &c, const std::vector<const void *> &srcs)
+// members: every member's source in active-set order (member_sources)
+void run_p2p(const Call &c, const std::vector<const void *> &members)
 {
     hipStream_t st = pe_stream(c.name, c.me);
+    std::vector<int> order(c.PE_size);
+    fold_order(c.me, c.PE_start, c.step, c.PE_size, order.data());
+    std::vector<const void *> srcs(c.PE_size);  // in this PE's fold order
+    for (int k = 0; k < c.PE_size; k++) srcs[k] = members[c.index_of(order[k])];
     t_last_path = OSGPU_RAN_PULL;
     // prior device work of this process that produced `source` must be done
     entry_sync(c.name, st);
     barrier(c);  // src/reductions.c:82 -- every source is ready
-    const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.source, c.nbytes);
-    void *out = overlap ? device_scratch(c.name, c.me, c.nbytes) : c.target;
-    hipError_t e = osgpu::launch_combine(c.type, c.op, out, srcs.data(), c.PE_size,
-                                         (size_t) c.nreduce, st);
-    if (e != hipSuccess) fatal(c.name, "combine launch: %s", hipGetErrorString(e));
+    const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const DeviceOut out(c, c.target, overlap, c.nbytes);
+    launched(c.name, "combine launch",
+             osgpu::launch_combine(c.type, c.op, out.out, srcs.data(), c.PE_size,
+                                   (size_t) c.nreduce, st));
     stream_wait(c.name, st);
     barrier(c);  // src/reductions.c:113 -- peers are done reading my source
-    if (overlap) {
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.nbytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.nbytes, st);
 }
 
 // ---------------------------------------------------- fused small calls
@@ -353,18 +337,14 @@ void run_fused(const Call &c, SyncSet &S, const std::vector<const void *> &srcs,
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
     const int P = c.PE_size, idx = S.idx;
-    osgpu::FusedArgs a;
-    memset(&a, 0, sizeof(a));
+    osgpu::FusedArgs a = fused_args(c, S);
     long long lo = 0, hi = c.nreduce;
-    if (team) osgpu_shard_range(c.nreduce, P, idx, (int) (s > 16 ? 16 : s), &lo, &hi);
+    if (team) shard_of(c.nreduce, P, idx, s, &lo, &hi);
     // (staged form: target and source may overlap -- the source is copied
     // into staging before any member writes, the target after all are done)
-    const bool overlap = !G && !team && ranges_overlap(c.target, c.source, c.nbytes);
-    void *out = overlap ? device_scratch(c.name, c.me, c.nbytes) : c.target;
-    for (int i = 0; i < P; i++) {
-        a.src[i] = (const char *) srcs[i] + (size_t) lo * s;
-        a.flags[i] = S.peer[i];
-    }
+    const bool overlap = !G && !team && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const DeviceOut out(c, c.target, overlap, c.nbytes);
+    for (int i = 0; i < P; i++) a.src[i] = (const char *) srcs[i] + (size_t) lo * s;
     if (team) {
         for (int d = 0; d < P; d++) {
             a.dst[d] = (char *) dsts[d] + (size_t) lo * s;
@@ -372,18 +352,11 @@ void run_fused(const Call &c, SyncSet &S, const std::vector<const void *> &srcs,
         }
         a.D = P;
     } else {
-        a.dst[0] = out;
+        a.dst[0] = out.out;
         a.q[0] = idx;
         a.D = 1;
     }
-    a.mine = S.local;
-    a.err = S.err_d;
-    a.done_host = S.done_d;
-    a.epoch = ++S.epoch;
     a.n = (size_t) (hi - lo);
-    a.P = P;
-    a.me = idx;
-    a.max_blocks = S.max_blocks;
     if (G) {
         a.host_in = host_in;
         a.host_out = host_out;
@@ -405,17 +378,13 @@ void run_fused(const Call &c, SyncSet &S, const std::vector<const void *> &srcs,
     }();
     a.trace = trace;
     if (trace) memset(trace, 0, 64);  // slots a continuation launch leaves unwritten stay 0
-    entry_order(c.name, st);
-    if (!fused_complete(c.name, S, st, a, [&](const osgpu::FusedArgs &x) {
+    if (!fused_run(c, S, st, a, [&](const osgpu::FusedArgs &x) {
             return osgpu::launch_fused(c.type, c.op, x, st);
         })) {
         t_last_path = OSGPU_RAN_FUSED_FAILED;
         return;
     }
-    if (overlap) {  // every reader of my source is done: the call passed its exit barrier
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.nbytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.nbytes, st);  // every reader of my source is done: the call passed its exit barrier
     if (trace && osgpu_last_continuations() > 0) {
         // the phase clocks are taken by the first launch only (fused.hip):
         // a call that needed continuations has no consistent breakdown
@@ -471,11 +440,7 @@ bool rccl_usable(const Call &c, bool forced)
     ncclDataType_t dt;
     ncclRedOp_t rop;
     size_t mult;
-    // the whole job only: a subset communicator would need ncclCommSplit,
-    // which every PE of the parent must call -- OpenSHMEM forbids
-    // non-members from calling a collective on an active set
-    return g_rccl.world && c.PE_start == 0 && c.step == 1 && c.PE_size == g_rccl.npes &&
-           c.me == g_rccl.me && rccl_types(c.type, c.op, forced, &dt, &rop, &mult);
+    return rccl_whole_job(c) && rccl_types(c.type, c.op, forced, &dt, &rop, &mult);
 }
 
 void run_rccl(const Call &c)
@@ -487,16 +452,14 @@ void run_rccl(const Call &c)
     t_last_path = OSGPU_RAN_RCCL;
     hipStream_t st = pe_stream(c.name, c.me);
     entry_sync(c.name);
-    const bool overlap = ranges_overlap(c.target, c.source, c.nbytes) && c.target != c.source;
-    void *out = overlap ? device_scratch(c.name, c.me, c.nbytes) : c.target;
-    ncclResult_t r = ncclAllReduce(c.source, out, (size_t) c.nreduce * mult, dt, rop,
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes) &&
+                         c.target != c.source;
+    const DeviceOut out(c, c.target, overlap, c.nbytes);
+    ncclResult_t r = ncclAllReduce(c.source, out.out, (size_t) c.nreduce * mult, dt, rop,
                                    g_rccl.world, st);
     if (r != ncclSuccess) fatal(c.name, "ncclAllReduce: %s", ncclGetErrorString(r));
     stream_wait(c.name, st);
-    if (overlap) {
-        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.nbytes, hipMemcpyDeviceToDevice, st));
-        stream_wait(c.name, st);
-    }
+    out.finish(c.nbytes, st);
 }
 
 // How the STAGED path moves its chunks across PCIe (OSGPU_STAGE_COPY):
@@ -528,7 +491,7 @@ void stage_leg(const char *name, int mode, void *dst, const void *src, size_t by
     else
         e = hipMemcpyAsync(dst, src, bytes, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice,
                            st);
-    if (e != hipSuccess) fatal(name, "staging copy: %s", hipGetErrorString(e));
+    launched(name, "staging copy", e);
 }
 
 void run_staged(const Call &c, StageSet &S)
@@ -538,13 +501,11 @@ void run_staged(const Call &c, StageSet &S)
     const size_t N = (size_t) c.nreduce;
     const size_t nchunks = (N + C - 1) / C;
     t_last_path = OSGPU_RAN_STAGED;
-    const int P = c.PE_size;
-    int idx = 0;
-    for (int i = 0, pe = c.PE_start; i < P; i++, pe += c.step)
-        if (pe == c.me) idx = i;
-    const bool overlap = ranges_overlap(c.target, c.source, c.nbytes) && c.target != c.source;
-    char *result = overlap ? (char *) malloc(c.nbytes) : (char *) c.target;
-    if (!result) fatal(c.name, "out of memory for the temporary target");
+    const int P = c.PE_size, idx = c.index_of(c.me);
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes) &&
+                         c.target != c.source;
+    HostTmp tmp(c, c.target, overlap, c.nbytes);
+    char *result = tmp.out;
     const char *src = (const char *) c.source;
     std::vector<const void *> sp(P);
     std::vector<void *> dp(P);
@@ -588,7 +549,7 @@ void run_staged(const Call &c, StageSet &S)
     h2d(0);
     for (size_t ch = 0; ch < nchunks; ch++) {
         const int sl = (int) (ch & 1);
-        const size_t n = (ch + 1) * C <= N ? C : N - ch * C;
+        const size_t n = chunk_n(ch);
         if (ch + 1 < nchunks) h2d(ch + 1);   // slot reuse is safe: team(ch-1) ended everywhere
         HIPCHK(c.name, hipEventSynchronize(S.ev_in[sl]));
         if (ch >= 2) {  // my out slot (and its bounce) drained
@@ -598,27 +559,25 @@ void run_staged(const Call &c, StageSet &S)
         barrier(c);  // chunk ch staged on every PE, every out[sl] free
         if (P == 1) {
             const void *one = S.in(0, sl);
-            hipError_t e = osgpu::launch_combine(c.type, c.op, S.out(0, sl), &one, 1, n, S.st_c);
-            if (e != hipSuccess) fatal(c.name, "combine launch: %s", hipGetErrorString(e));
+            launched(c.name, "combine launch",
+                     osgpu::launch_combine(c.type, c.op, S.out(0, sl), &one, 1, n, S.st_c));
         } else if (P <= osgpu::kMaxTeam) {
             long long lo = 0, hi = 0;
-            osgpu_shard_range((long long) n, P, idx, (int) (s > 16 ? 16 : s), &lo, &hi);
+            shard_of((long long) n, P, idx, s, &lo, &hi);
             for (int i = 0; i < P; i++) {
                 sp[i] = S.in(i, sl) + (size_t) lo * s;
                 dp[i] = S.out(i, sl) + (size_t) lo * s;
             }
-            if (hi > lo) {
-                hipError_t e = osgpu::launch_team(c.type, c.op, P, dp.data(), sp.data(),
-                                                  (size_t) (hi - lo), S.st_c, S.ndev > 1);
-                if (e != hipSuccess) fatal(c.name, "team launch: %s", hipGetErrorString(e));
-            }
+            if (hi > lo)
+                launched(c.name, "team launch",
+                         osgpu::launch_team(c.type, c.op, P, dp.data(), sp.data(),
+                                            (size_t) (hi - lo), S.st_c, S.ndev > 1));
         } else {  // large active sets: every PE folds its own chunk (pull form)
             std::vector<int> order(P);
             fold_order(c.me, c.PE_start, c.step, P, order.data());
             for (int k = 0; k < P; k++) sp[k] = S.in((order[k] - c.PE_start) / c.step, sl);
-            hipError_t e = osgpu::launch_combine(c.type, c.op, S.out(idx, sl), sp.data(), P, n,
-                                                 S.st_c);
-            if (e != hipSuccess) fatal(c.name, "combine launch: %s", hipGetErrorString(e));
+            launched(c.name, "combine launch",
+                     osgpu::launch_combine(c.type, c.op, S.out(idx, sl), sp.data(), P, n, S.st_c));
         }
         stream_wait(c.name, S.st_c);
         barrier(c);  // every shard of my out[sl] written
@@ -628,10 +587,7 @@ void run_staged(const Call &c, StageSet &S)
     }
     stream_wait(c.name, S.st_out);
     for (size_t ch = nchunks >= 2 ? nchunks - 2 : 0; ch < nchunks; ch++) drain(ch);
-    if (overlap) {
-        memcpy(c.target, result, c.nbytes);
-        free(result);
-    }
+    tmp.finish(c.nbytes);
 }
 
 // Host symmetric-heap arguments: the data arrives and leaves through host
@@ -640,10 +596,6 @@ void run_staged(const Call &c, StageSet &S)
 // chunks into pinned staging, then combined on the GPU.
 void run_host(const Call &c)
 {
-    if (!c.ops.getmem) fatal(c.name, "host-memory arguments need shmem_getmem");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        fatal(c.name, "no GPU visible: the combine runs only on the GPU");
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
     const int P = c.PE_size;
@@ -659,9 +611,8 @@ void run_host(const Call &c)
     // device: P input slots + 1 output slot; pinned: P input slots + output
     char *dbuf = (char *) device_scratch(c.name, c.me, cb * (P + 1));
     char *hbuf = (char *) host_stage(c.name, c.me, cb * (P + 1));
-    const bool overlap = P > 1 && ranges_overlap(c.target, c.source, c.nbytes);
-    char *result = overlap ? (char *) malloc(c.nbytes) : (char *) c.target;
-    if (!result) fatal(c.name, "out of memory for the temporary target");
+    const bool overlap = P > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    HostTmp result(c, c.target, overlap, c.nbytes);
     std::vector<const void *> srcs(P);
     for (int k = 0; k < P; k++) srcs[k] = dbuf + (size_t) k * cb;
 
@@ -677,18 +628,15 @@ void run_host(const Call &c)
             HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
         }
         char *dout = dbuf + (size_t) P * cb;
-        hipError_t e = osgpu::launch_combine(c.type, c.op, dout, srcs.data(), P, n, st);
-        if (e != hipSuccess) fatal(c.name, "combine launch: %s", hipGetErrorString(e));
+        launched(c.name, "combine launch",
+                 osgpu::launch_combine(c.type, c.op, dout, srcs.data(), P, n, st));
         char *hout = hbuf + (size_t) P * cb;
         HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
         stream_wait(c.name, st);
-        memcpy(result + off * s, hout, nb);
+        memcpy(result.out + off * s, hout, nb);
     }
     barrier(c);  // src/reductions.c:113
-    if (overlap) {
-        memcpy(c.target, result, c.nbytes);  // src/reductions.c:114-119
-        free(result);
-    }
+    result.finish(c.nbytes);  // src/reductions.c:114-119
 }
 
 // Small calls on HOST symmetric-heap memory (each PE pulling at most
@@ -707,7 +655,7 @@ void run_host_fold(const Call &c)
     const int P = c.PE_size;
     std::vector<int> order(P);
     fold_order(c.me, c.PE_start, c.step, P, order.data());
-    const bool overlap = ranges_overlap(c.target, c.source, c.nbytes);
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
     thread_local std::vector<unsigned char> tmp, peer;
     if (overlap) tmp.resize(c.nbytes);
     void *acc = overlap ? (void *) tmp.data() : c.target;
@@ -736,8 +684,7 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
     c.nreduce = nreduce;
     if (nreduce <= 0) {  // nothing to combine; the collective still syncs
         t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        barrier(c);
-        barrier(c);
+        sync_only(c);
         return;
     }
     c.nbytes = type_size(type) * (size_t) nreduce;  // no int overflow (cf. :44)
@@ -748,10 +695,7 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
         fatal(name, "target and source must both be device or both be host memory");
     if (kt == MEM_HOST) {
         const int hp = host_path();
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            fatal(name, "no GPU visible: the combine runs only on the GPU");
-        if (!c.ops.getmem) fatal(name, "host-memory arguments need shmem_getmem");
+        require_host_heaps(c);
         // a size every member shares: all of them take the same path
         const size_t fold_lim = host_fold_max_bytes();  // 0: off
         if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && (size_t) (c.PE_size - 1) * c.nbytes <= fold_lim &&
@@ -781,9 +725,7 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
         }
         return;
     }
-    int cur = 0;
-    HIPCHK(name, hipGetDevice(&cur));
-    if (cur != dt) HIPCHK(name, hipSetDevice(dt));
+    const DeviceGuard on_device(name, dt);
     const int mode = path_mode();
     std::vector<const void *> srcs;
     std::vector<void *> dsts;
@@ -807,12 +749,10 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
         else
             run_team(c, srcs, dsts, idx, remote);
     } else if (member_sources(c, srcs)) {
-        if (fused_eligible(c, false) && (S = sync_setup(c))) {
+        if (fused_eligible(c, false) && (S = sync_setup(c)))
             run_fused(c, *S, srcs, dsts, false);
-        } else {
-            p2p_sources(c, srcs);
+        else
             run_p2p(c, srcs);
-        }
     } else if (mode == OSGPU_PATH_AUTO && rccl_usable(c, false)) {
         run_rccl(c);
     } else {
@@ -823,7 +763,6 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
               "(path mode %d)",
               mode);
     }
-    if (cur != dt) HIPCHK(name, hipSetDevice(cur));
 }
 
 }  // namespace

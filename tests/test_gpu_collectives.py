@@ -144,6 +144,52 @@ def test_collective_source_is_target(mode, kind):
                   same_buffer=True)
 
 
+@pytest.mark.parametrize("mode", ["device", "getmem", "staged"])
+@pytest.mark.parametrize("kind", ["fcollect", "alltoall"])
+@pytest.mark.parametrize("bits", [32, 64])
+def test_collective_target_one_element_after_source(mode, kind, bits):
+    """Partial overlap: the target starts one element after the source (at
+    nelems == 1 fcollect's two are adjacent).  Every block must carry the
+    members' sources as written BEFORE the call (scratch on the COPY path,
+    a temporary target on GETMEM and STAGED -- 256 B of staging per slot,
+    several chunks); the source's first element and the margins stay."""
+    P, esz, s_off = 3, bits // 8, 1024
+    L = osgpu.load()
+    if mode == "staged":
+        L.osgpu_finalize()
+        L.osgpu_set_stage_bytes(256)
+    try:
+        with host_path(mode):
+            for nelems in (1, 65):
+                nb = nelems * esz
+                per_src = nb * (P if kind == "alltoall" else 1)
+                t_off, tgt_bytes = s_off + esz, P * nb
+                lo, span = s_off - MARGIN, esz + tgt_bytes + 2 * MARGIN
+                tm = T.Team(P, lo + span, device=mode == "device")
+                src, exp = {}, {}
+                for pe in range(P):
+                    src[pe] = np.random.default_rng(bits * 977 + nelems * 31 + pe).integers(
+                        0, 256, per_src, dtype=np.uint8)
+                    exp[pe] = np.full(span, 0xA5, np.uint8)
+                    exp[pe][MARGIN:MARGIN + per_src] = src[pe]
+                    tm.write(pe, lo, exp[pe])
+                for me in range(P):
+                    for i in range(P):
+                        blk = src[i][:nb] if kind == "fcollect" else src[i][me * nb:(me + 1) * nb]
+                        exp[me][MARGIN + esz + i * nb:][:nb] = blk
+                tm.run_coll(kind, bits, t_off, s_off, nelems)
+                for pe in range(P):
+                    got = tm.read(pe, lo, span)
+                    bad = np.nonzero(got != exp[pe])[0]
+                    assert bad.size == 0, (nelems, pe, bad[:8], got[bad[:8]], exp[pe][bad[:8]])
+                want = {"device": "copy", "getmem": "getmem", "staged": "staged"}[mode]
+                assert set(tm.last_coll_paths.values()) == {want}, tm.last_coll_paths
+    finally:
+        if mode == "staged":
+            L.osgpu_finalize()
+            L.osgpu_set_stage_bytes(-1)
+
+
 @pytest.mark.parametrize("kind", ["broadcast", "collect", "fcollect", "alltoall"])
 def test_host_staged_many_chunks(kind):
     """16 KiB of staging per PE: thousands of chunks, ragged last chunk."""

@@ -192,6 +192,86 @@ def test_host_staged_matches_golden(torch_cuda, t, op, host_path, monkeypatch):
         L.osgpu_finalize()
 
 
+OVERLAP_PAIRS = [("int", "sum"), ("double", "sum"), ("longdouble", "sum"), ("short", "min")]
+OVERLAP_BASE = 4096   # heap offset of the lower of the two arrays
+OVERLAP_PAD = 256     # sentinel bytes checked on either side
+
+
+def _overlap_cases():
+    """(The golden grid has no nreduce == 257 case: 1 and 4097 are replayed.
+    At nreduce == 1 the two arrays are adjacent, at 4097 all but one element
+    of each overlaps the other.)"""
+    return [c for c in CASES if (c["type"], c["op"]) in OVERLAP_PAIRS and c["tag"] == "grid"
+            and c["nreduce"] in (1, 257, 4097) and c["npes"] in (2, 3)]
+
+
+def run_shifted(tm, c, after):
+    """The golden case with its target one element after (or before) its
+    source.  The result depends on the sources only: the members' targets
+    must carry the case's digests, every other byte around the two arrays
+    (the element of the source outside the target included) and the same
+    window of a non-member must be unchanged."""
+    t, op, n, P = c["type"], c["op"], c["nreduce"], c["npes"]
+    s = O.NP_DTYPE[t]().itemsize if t != "longdouble" else 16
+    nbytes = n * s
+    soff, toff = (OVERLAP_BASE, OVERLAP_BASE + s) if after else (OVERLAP_BASE + s, OVERLAP_BASE)
+    lo, span = OVERLAP_BASE - OVERLAP_PAD, nbytes + s + 2 * OVERLAP_PAD
+    src = O.case_inputs(c)
+    before = {}
+    for pe in range(P + 1):   # PE P is not a member
+        tm.fill(pe, lo, span, 0xA5)
+        tm.write(pe, soff, src[pe] if pe < P else src[0])
+        before[pe] = tm.read(pe, lo, span)
+    tm.run(t, op, toff, soff, n, c["PE_start"], c["logPE_stride"], c["PE_size"])
+    out = {}
+    for pe in range(P + 1):
+        got = tm.read(pe, lo, span)
+        if pe == P:
+            assert np.array_equal(got, before[pe]), f"non-member PE {pe} was written"
+            continue
+        a, b = toff - lo, toff - lo + nbytes
+        assert np.array_equal(got[:a], before[pe][:a]), (t, op, P, n, after, pe, "below target")
+        assert np.array_equal(got[b:], before[pe][b:]), (t, op, P, n, after, pe, "above target")
+        raw = got[a:b]
+        out[pe] = O.from_value_bytes(t, raw if t != "longdouble" else
+                                     raw.reshape(-1, 16)[:, :10].reshape(-1))
+    return out
+
+
+@pytest.mark.parametrize("after", [True, False], ids=["target_after", "target_before"])
+@pytest.mark.parametrize("mode", ["device", "staged", "getmem", "host_fold"])
+def test_target_shifted_one_element_against_source(torch_cuda, mode, after):
+    """Partial overlap: the target starts one element after its source, and
+    one element before it.  Device heaps: the pull form (the team form
+    refuses overlap) into scratch, copied after the exit barrier; host heaps
+    under STAGED (4 KiB stage bytes) and GETMEM (4 KiB chunks) through a
+    temporary target, and the host fold through its own.  Bit-exact against
+    the golden digests."""
+    L = osgpu.load()
+    cases = _overlap_cases()
+    assert len(cases) >= 16
+    if mode in ("staged", "getmem"):
+        L.osgpu_set_host_chunk_bytes(4096)
+        L.osgpu_set_stage_bytes(4096)
+        L.osgpu_finalize()  # staging is sized at set-up
+    try:
+        with osgpu.host_path(mode if mode in ("staged", "getmem") else None):
+            tm = team(device=mode == "device", host_fold=mode == "host_fold")
+            for c in cases:
+                check(c, run_shifted(tm, c, after))
+                if mode == "device":   # adjacent at nreduce == 1: no overlap, team form
+                    want = {"pull" if c["nreduce"] > 1 else "team"}
+                else:
+                    want = {mode}
+                act = O.active_set(c["PE_start"], c["logPE_stride"], c["PE_size"])
+                assert {tm.last_paths[pe] for pe in act} == want, (tm.last_paths, want)
+    finally:
+        if mode in ("staged", "getmem"):
+            L.osgpu_set_host_chunk_bytes(-1)
+            L.osgpu_set_stage_bytes(-1)
+            L.osgpu_finalize()
+
+
 @pytest.mark.parametrize("t,op", sorted({(c["type"], c["op"]) for c in CASES}))
 def test_host_fold_matches_golden(torch_cuda, t, op):
     """The library's default for small HOST symmetric-heap calls (each PE
