@@ -660,6 +660,11 @@ void run_host_fold(const Call &c)
     if (overlap) tmp.resize(c.nbytes);
     void *acc = overlap ? (void *) tmp.data() : c.target;
     memcpy(acc, c.source, c.nbytes);  // :79-81
+    // long double: bytes 10..15 of every written slot are zero on every path
+    // (longdouble.hip).  The folds below write them so; a set of one PE has
+    // no fold, and the copy would carry the source's padding into the target
+    if (c.type == osgpu::T_LONGDOUBLE && P == 1)
+        for (size_t i = 0; i < (size_t) c.nreduce; i++) memset((char *) acc + 16 * i + 10, 0, 6);
     barrier(c);                       // :82 -- every source is ready
     peer.resize(c.nbytes);
     for (int k = 1; k < P; k++) {     // order[0] is this PE

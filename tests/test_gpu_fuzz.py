@@ -21,6 +21,7 @@ import pytest
 
 import oracle as O
 import osgpu
+from support import guarded
 
 HEAP = 8 << 20
 NCASE = int(os.environ.get("OSGPU_FUZZ_CASES", "800"))
@@ -94,10 +95,22 @@ def run_case(c):
     assert c["toff"] + max(nbytes, 16) <= HEAP and c["soff"] + nbytes <= HEAP
     src = O.team_inputs(t, 8, n, c["seed"], c["dist"])
     act = O.active_set(c["start"], c["stride"], c["size"])
+    # the frame around the target, members' too: the position-varying band
+    # pattern (tests/support/guarded.py) over the 4096 free bytes before the
+    # target and after it -- past the 0x5A fill -- to the next 4 KiB
+    # boundary, at least 64 bytes, inside the heap
+    b0 = c["toff"] - 4096
+    assert b0 >= 0 and (c["in_place"] or c["soff"] + nbytes <= b0)
+    a0 = c["toff"] + (nbytes if c["in_place"] else max(nbytes, 16))
+    end = c["toff"] + nbytes
+    a1 = (end // 4096 + 1) * 4096
+    a1 = max(a0, min(a1 if a1 - end >= 64 else a1 + 4096, HEAP))
     for pe in range(8):
         tm.write(pe, c["soff"], src[pe])
         if not c["in_place"]:
             tm.fill(pe, c["toff"], max(nbytes, 16), 0x5A)
+        tm.write(pe, b0, guarded.pattern(b0, 4096))
+        tm.write(pe, a0, guarded.pattern(a0, a1 - a0))
     before = {pe: tm.read(pe, c["soff"], nbytes).copy() for pe in range(8)}
     L = osgpu.load()
     L.osgpu_set_path(c["path"])
@@ -107,7 +120,18 @@ def run_case(c):
         L.osgpu_set_path(osgpu.PATH_AUTO)
     want = O.to_all(t, c["op"], src, c["start"], c["stride"], c["size"])
     for pe in range(8):
+        win = tm.read(pe, b0, a1 - b0)
+        d = guarded.first_diff(win[:4096], guarded.pattern(b0, 4096))
+        assert d is None, f"case {c}: PE {pe}: byte {d - 4096} before the target was written"
+        mid = win[4096 + nbytes:a0 - b0]
+        assert c["in_place"] or (mid == 0x5A).all(), \
+            f"case {c}: PE {pe}: the bytes just after the target were written"
+        d = guarded.first_diff(win[a0 - b0:], guarded.pattern(a0, a1 - a0))
+        assert d is None, f"case {c}: PE {pe}: byte +{a0 - end + d + 1} after the target was written"
         if pe in act:
+            if t == "longdouble":
+                assert not win[4096:4096 + nbytes].reshape(-1, 16)[:, 10:].any(), \
+                    f"case {c}: PE {pe}: bytes 10..15 of a written long double slot are not zero"
             got = value_view(t, tm.read(pe, c["toff"], nbytes))
             assert np.array_equal(O.value_bytes(got), O.value_bytes(want[pe])), \
                 f"case {c}: PE {pe} differs from the oracle"

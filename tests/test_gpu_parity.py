@@ -18,6 +18,7 @@ import pytest
 
 import oracle as O
 import osgpu
+from support import guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -52,27 +53,57 @@ def tgt_off(nbytes):
     return max(4096, (nbytes + 4095) // 4096 * 4096)
 
 
+def frame_end(end):
+    """Where the band after a target ending at heap offset `end` stops: the
+    next 4 KiB boundary past it, at least 64 bytes on."""
+    hi = (end // 4096 + 1) * 4096
+    return hi if hi - end >= 64 else hi + 4096
+
+
 def run_case(tm, c, in_place=False):
     t, op, n = c["type"], c["op"], c["nreduce"]
     s = O.NP_DTYPE[t]().itemsize if t != "longdouble" else 16
     nbytes = n * s
     src = O.case_inputs(c)
     toff = 0 if in_place else tgt_off(nbytes)
+    # the frame around the target, members' too: the position-varying band
+    # pattern (tests/support/guarded.py) in the free gap between the source
+    # and the target (none in place) and after the target -- past the 0xA5
+    # fill -- to the next 4 KiB boundary, at least 64 bytes, inside the heap
+    a0 = toff + (nbytes if in_place else max(nbytes, 16))
+    a1 = max(a0, min(frame_end(toff + nbytes), tm.psync_off))
     for pe in range(c["npes"]):
         tm.write(pe, 0, src[pe])
         if not in_place:
             tm.fill(pe, toff, max(nbytes, 16), 0xA5)
+            tm.write(pe, nbytes, guarded.pattern(nbytes, toff - nbytes))
+        tm.write(pe, a0, guarded.pattern(a0, a1 - a0))
     tm.run(t, op, toff, 0, n, c["PE_start"], c["logPE_stride"], c["PE_size"])
     act = O.active_set(c["PE_start"], c["logPE_stride"], c["PE_size"])
     out = {}
+    who = f"{t}/{op} P={c['npes']} N={n} {c['tag']} start={c['PE_start']} in_place={in_place}"
     for pe in range(c["npes"]):
         raw = tm.read(pe, toff, nbytes)
         if pe in act:
             out[pe] = O.from_value_bytes(t, raw if t != "longdouble" else
                                          raw.reshape(-1, 16)[:, :10].reshape(-1))
+            if t == "longdouble":
+                assert not raw.reshape(-1, 16)[:, 10:].any(), \
+                    f"{who}: PE {pe}: bytes 10..15 of a written long double slot are not zero"
         elif not in_place:
             assert (tm.read(pe, toff, max(nbytes, 16)) == 0xA5).all(), \
                 f"non-member PE {pe} target was written"
+        win = tm.read(pe, 0, a1)
+        if not in_place or pe not in act:
+            assert np.array_equal(win[:nbytes], np.ascontiguousarray(src[pe]).view(np.uint8)
+                                  .reshape(-1)), f"{who}: PE {pe}'s source was modified"
+        if not in_place:
+            d = guarded.first_diff(win[nbytes:toff], guarded.pattern(nbytes, toff - nbytes))
+            assert d is None, f"{who}: PE {pe}: byte {d - (toff - nbytes)} before the target was written"
+            assert (win[toff + nbytes:a0] == 0xA5).all(), \
+                f"{who}: PE {pe}: the bytes just after the target were written"
+        d = guarded.first_diff(win[a0:a1], guarded.pattern(a0, a1 - a0))
+        assert d is None, f"{who}: PE {pe}: byte +{a0 - toff - nbytes + d + 1} after the target was written"
     return out
 
 
