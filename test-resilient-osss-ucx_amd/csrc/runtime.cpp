@@ -25,6 +25,7 @@
 
 #include "../../include/osgpu_reduce.h"
 #include "combine.hpp"
+#include "psync_board.hpp"
 #include "runtime.hpp"
 
 namespace osgpu {
@@ -661,8 +662,6 @@ void par_memcpy(void *dst, const void *src, size_t n)
 // and reads the peers' with shmem_getmem; pSync is returned zeroed.
 // ---------------------------------------------------------------------
 
-constexpr int kPsyncBase = 16;  // pSync[16..28] used during setup only
-
 std::map<std::tuple<int, int, int, int, int>, StageSet> g_stage;  // (me, set, device)
 
 long long g_stage_bytes = -1;  // osgpu_set_stage_bytes; -1: OSGPU_STAGE_BYTES, 32 MiB
@@ -685,8 +684,6 @@ struct StageMsg {  // what a PE publishes in pSync[16..30]
     long handle[OSGPU_IPC_HANDLE_BYTES / sizeof(long)];
     long raw_ptr, pid, slot, status, pci, pad[2];
 };
-// the smallest pSync a caller hands us: SHMEM_BCAST/COLLECT/ALLTOALL_SYNC_SIZE
-static_assert(sizeof(StageMsg) <= (64 - kPsyncBase) * sizeof(long), "pSync room");
 
 long pci_key(int dev)
 {
@@ -710,8 +707,8 @@ bool map_members(const Coll &c, char *local, size_t bytes, std::vector<char *> &
 {
     int dev = 0;
     HIPCHK(c.name, hipGetDevice(&dev));
-    StageMsg *mine = reinterpret_cast<StageMsg *>(c.pSync + kPsyncBase);
-    memset(mine, 0, sizeof(*mine));
+    PsyncBoard<StageMsg> board(c);
+    StageMsg *mine = &board.mine();
     hipIpcMemHandle_t h;
     if (local && hipIpcGetMemHandle(&h, local) == hipSuccess) memcpy(mine->handle, &h, sizeof(h));
     else (void) hipGetLastError();
@@ -719,18 +716,17 @@ bool map_members(const Coll &c, char *local, size_t bytes, std::vector<char *> &
     mine->pid = (long) getpid();
     mine->slot = local ? (long) bytes : -1;
     mine->pci = pci_key(dev);
-    barrier(c);
+    board.publish();
     bool ok = local != nullptr;
     peer.assign(c.PE_size, nullptr);
     std::vector<long> pcis(1, mine->pci), all_pci(1, mine->pci);
     std::vector<long> pids_here(1, mine->pid);  // processes on my GPU
-    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step) {
-        if (pe == c.me) {
+    for (int i = 0; i < c.PE_size; i++) {
+        if (c.pe_at(i) == c.me) {
             peer[i] = local;
             continue;
         }
-        StageMsg m;
-        c.ops.getmem(&m, mine, sizeof(m), pe);
+        const StageMsg m = board.read(i);
         all_pci.push_back(m.pci);
         if (std::find(pcis.begin(), pcis.end(), m.pci) == pcis.end()) pcis.push_back(m.pci);
         if (m.pci == mine->pci &&
@@ -754,17 +750,9 @@ bool map_members(const Coll &c, char *local, size_t bytes, std::vector<char *> &
             }
         }
     }
-    mine->status = ok ? 1 : 2;
-    barrier(c);
-    bool all_ok = ok;
-    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step) {
-        if (pe == c.me) continue;
-        long st = 0;
-        c.ops.getmem(&st, &mine->status, sizeof(long), pe);
-        all_ok = all_ok && st == 1;
-    }
-    barrier(c);
-    memset(mine, 0, sizeof(*mine));  // pSync back to SHMEM_SYNC_VALUE
+    bool all_ok = true;
+    for (long st : board.post_status(&StageMsg::status, ok ? 1 : 2)) all_ok = all_ok && st == 1;
+    board.close();
     if (ndev) *ndev = (int) pcis.size();
     if (procs_here) *procs_here = (int) pids_here.size();
     if (max_share) {

@@ -15,6 +15,7 @@
 #include <functional>
 #include <vector>
 
+#include "coll.hpp"
 #include "combine.hpp"
 
 namespace osgpu {
@@ -22,22 +23,9 @@ namespace rt {
 
 // ------------------------------------------------------------------ errors
 
-void set_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// set_err, debug_level and DBG: coll.hpp
 [[noreturn]] void fatal(const char *where, const char *fmt, ...)
     __attribute__((format(printf, 2, 3)));
-int debug_level();
-
-// OSGPU_DEBUG=1: one stderr line per protocol step (call entry, path,
-// barriers, launches, syncs) -- for diagnosing multi-process runs
-#define DBG(...)                                                               \
-    do {                                                                       \
-        if (::osgpu::rt::debug_level() > 0) {                                  \
-            fprintf(stderr, "[osgpu pid %d] ", (int) getpid());                \
-            fprintf(stderr, __VA_ARGS__);                                      \
-            fputc('\n', stderr);                                               \
-            fflush(stderr);                                                    \
-        }                                                                      \
-    } while (0)
 
 #define HIPCHK(where, call)                                                    \
     do {                                                                       \
@@ -65,12 +53,6 @@ bool has_ext_op(int t, int op);
 
 // ------------------------------------------------------------- PE services
 
-struct PeOps {
-    int (*my_pe)(void) = nullptr;
-    int (*n_pes)(void) = nullptr;
-    void (*barrier)(int, int, int, long *) = nullptr;
-    void (*getmem)(void *, const void *, size_t, int) = nullptr;
-};
 PeOps pe_ops();
 
 // -------------------------------------------------------- device sym. heap
@@ -117,28 +99,9 @@ void fold_order(int me, int PE_start, int step, int PE_size, int *order);
 
 // ------------------------------------------------------------ active sets
 
-// One collective call on an active set (PE_start, 2^logPE_stride, PE_size).
-struct Coll {
-    const char *name = nullptr;
-    int PE_start = 0, logPE_stride = 0, PE_size = 0;
-    long *pSync = nullptr;
-    int me = -1, step = 1;
-    PeOps ops;
-    // index of PE `pe` in the active set, or -1
-    int index_of(int pe) const
-    {
-        if (pe < PE_start || (pe - PE_start) % step) return -1;
-        const int i = (pe - PE_start) / step;
-        return i < PE_size ? i : -1;
-    }
-    int pe_at(int i) const { return PE_start + i * step; }
-};
-
 // Fills name/active set/pSync/me/ops; aborts on an invalid active set or a
 // missing runtime (the shared entry checks of every collective).
 Coll make_coll(const char *name, int PE_start, int logPE_stride, int PE_size, long *pSync);
-
-void barrier(const Coll &c);
 
 // ---------------------------------------------------------- host staging
 

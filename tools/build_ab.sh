@@ -24,7 +24,7 @@ while [ $# -ge 2 ]; do
   wait
   for f in combine team fused longdouble; do [ -f $d/$f.o ] || cp $f.o $d/$f.o; done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libosgpu_reduce.so \
-      $d/combine.o $d/team.o $d/fused.o verify.o $d/longdouble.o copy.o host_fold.o runtime.o heap.o \
+      $d/combine.o $d/team.o $d/fused.o verify.o $d/longdouble.o copy.o host_fold.o runtime.o heap.o fd_channel.o \
       shmem_reduce.o shmem_collect.o -lrccl -ldl -lpthread
   rm -f $d/*.o
   echo "built tools/ab/$name"

@@ -23,7 +23,7 @@ CSRC = os.path.join(ROOT, "test-resilient-osss-ucx_amd", "csrc")
 VAR = os.path.join(ROOT, "tools", "variants")
 FL = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
       "-fno-fast-math"]
-OTHERS = ["team.o", "fused.o", "verify.o", "longdouble.o", "copy.o", "runtime.o", "heap.o",
+OTHERS = ["team.o", "fused.o", "verify.o", "longdouble.o", "copy.o", "runtime.o", "heap.o", "fd_channel.o",
           "shmem_reduce.o", "shmem_collect.o"]
 
 

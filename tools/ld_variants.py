@@ -26,7 +26,7 @@ CSRC = os.path.join(ROOT, "test-resilient-osss-ucx_amd", "csrc")
 VAR = os.path.join(ROOT, "tools", "variants")
 FL = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
       "-fno-fast-math"]
-OTHERS = ["combine.o", "team.o", "fused.o", "verify.o", "copy.o", "host_fold.o", "runtime.o", "heap.o",
+OTHERS = ["combine.o", "team.o", "fused.o", "verify.o", "copy.o", "host_fold.o", "runtime.o", "heap.o", "fd_channel.o",
           "shmem_reduce.o", "shmem_collect.o"]
 
 

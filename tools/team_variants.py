@@ -54,7 +54,7 @@ COPY_VARIANTS = {
     "blocked": "git:281a986",   # ranges one after another (before round 3's round-robin)
     "roundrobin": None,         # the tree's copy.hip
 }
-OTHERS = ["fused.o", "verify.o", "longdouble.o", "copy.o", "runtime.o", "heap.o",
+OTHERS = ["fused.o", "verify.o", "longdouble.o", "copy.o", "runtime.o", "heap.o", "fd_channel.o",
           "shmem_reduce.o", "shmem_collect.o"]
 
 
@@ -357,7 +357,7 @@ def run_place():
 
 def build_copy():
     subprocess.run(["make", "-s", "-j8"], cwd=CSRC, check=True)
-    others = ["combine.o", "team.o", "fused.o", "verify.o", "longdouble.o", "runtime.o", "heap.o",
+    others = ["combine.o", "team.o", "fused.o", "verify.o", "longdouble.o", "runtime.o", "heap.o", "fd_channel.o",
               "shmem_reduce.o", "shmem_collect.o"]
     for name, rev in COPY_VARIANTS.items():
         d = os.path.join(VAR, "copy_" + name)
