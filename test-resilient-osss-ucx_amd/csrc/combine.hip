@@ -211,6 +211,116 @@ __global__ __launch_bounds__(64 * K) void combine_lds_kernel(T *out, Inputs<T, K
     }
 }
 
+// Shifted form of combine_lds_kernel (launch_combine_shifted): every pointer
+// at its own 16-byte phase, each a multiple of sizeof(T) -- block m of a
+// symmetric source against a target at its own address (the reduce-scatter).
+// The target's 16-byte vectors tile the call as above.  Input k's bytes of
+// target vector j start sh_k = (in_k + head) & 15 bytes into ITS aligned
+// vector j, so wave k streams the tile's V aligned vectors of input k plus,
+// when sh_k != 0, the one after them (the halo: 16 B per input per tile)
+// into its LDS row of V + 1 slots; the fold reads input k at byte 16 j + sh_k
+// of row k.  Every global access of the body is an aligned 16-byte one.
+// The launcher keeps every aligned vector inside [in_k, in_k + n): a first
+// or last target vector whose cover would start before an input or end past
+// it goes to the element-wise edges.
+//
+// The read at the shift: slots j and j + 1 as two aligned 16-byte reads, the
+// 16 bytes picked out of the 32 in registers (sh_k is wave-uniform: one of
+// four static dword selections, v_alignbyte for the 2-byte types).  A
+// 16-byte LDS read off its alignment is not an option: it is replayed at 64
+// cycles per wave-instruction.  Reads at the element's own alignment (two
+// 8-byte, four 4-byte, five 4-byte + v_alignbyte) timed the same within
+// 0.5 % and are gone (tools/rscatter_rate.py, profiles/rscatter_rate.md:
+// U = 2 is 4 % ahead of U = 4 and 6 % ahead of U = 1).  An input at shift 0
+// (the fed-back target of a second chunk always is) takes one aligned read.
+#ifndef OSGPU_SHIFT_U
+#define OSGPU_SHIFT_U 2  // vectors per lane per input, every K
+#endif
+
+// bytes [sh, sh + 16) of lo:hi; sh wave-uniform, a multiple of E = sizeof(T)
+template <int E>
+__device__ __forceinline__ u32x4 shift_pair(u32x4 lo, u32x4 hi, unsigned sh)
+{
+    const unsigned x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    u32x4 r;
+    if constexpr (E == 8) {  // sh is 0 or 8
+        r = sh ? u32x4{x[2], x[3], x[4], x[5]} : lo;
+    } else if constexpr (E == 4) {
+        switch (sh >> 2) {
+        case 1: r = u32x4{x[1], x[2], x[3], x[4]}; break;
+        case 2: r = u32x4{x[2], x[3], x[4], x[5]}; break;
+        case 3: r = u32x4{x[3], x[4], x[5], x[6]}; break;
+        default: r = lo; break;
+        }
+    } else {
+        const unsigned b = sh & 3;
+#define OSGPU_AB(i) __builtin_amdgcn_alignbyte(x[(i) + 1], x[i], b)
+        switch (sh >> 2) {
+        case 0: r = u32x4{OSGPU_AB(0), OSGPU_AB(1), OSGPU_AB(2), OSGPU_AB(3)}; break;
+        case 1: r = u32x4{OSGPU_AB(1), OSGPU_AB(2), OSGPU_AB(3), OSGPU_AB(4)}; break;
+        case 2: r = u32x4{OSGPU_AB(2), OSGPU_AB(3), OSGPU_AB(4), OSGPU_AB(5)}; break;
+        default: r = u32x4{OSGPU_AB(3), OSGPU_AB(4), OSGPU_AB(5), OSGPU_AB(6)}; break;
+        }
+#undef OSGPU_AB
+    }
+    return r;
+}
+
+// the 16 bytes at byte 16 j + sh of an LDS row
+template <typename T>
+__device__ __forceinline__ u32x4 read_shifted(const u32x4 *row, int j, unsigned sh)
+{
+    if (sh == 0) return row[j];
+    return shift_pair<(int) sizeof(T)>(row[j], row[j + 1], sh);
+}
+
+template <typename T, int OP, int K, int U>
+__global__ __launch_bounds__(64 * K) void combine_shift_kernel(T *out, Inputs<T, K> in, size_t nvec,
+                                                                size_t head, size_t tail_start,
+                                                                int nedge)
+{
+    constexpr int V = 64 * U;  // target vectors per tile
+    __shared__ u32x4 tile[K][V + 1];
+    if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
+        const size_t e = edge_index(head, tail_start);
+        out[e] = fold_scalar<T, OP, K>(in, e);
+    }
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63);
+    const size_t base = (size_t) blockIdx.x * V;
+    const bool whole = base + V <= nvec;
+    const int cnt = whole ? V : (base < nvec ? (int) (nvec - base) : 0);  // this tile's vectors
+    const T *pw = in.p[0];
+#pragma unroll
+    for (int k = 1; k < K; k++)
+        if (w == k) pw = in.p[k];
+    const uintptr_t at = reinterpret_cast<uintptr_t>(pw + head);
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(at - (at & 15)) + base;
+    const bool halo = (at & 15) != 0 && lane == 0 && cnt > 0;
+    u32x4 v[U], h = {};
+#pragma unroll
+    for (int u = 0; u < U; u++)
+        if (u * 64 + lane < cnt) v[u] = __builtin_nontemporal_load(src + u * 64 + lane);
+    if (halo) h = __builtin_nontemporal_load(src + cnt);
+#pragma unroll
+    for (int u = 0; u < U; u++)
+        if (u * 64 + lane < cnt) tile[w][u * 64 + lane] = v[u];
+    if (halo) tile[w][cnt] = h;
+    __syncthreads();
+    unsigned sh[K];
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        sh[k] = (unsigned) (reinterpret_cast<uintptr_t>(in.p[k] + head) & 15);
+    u32x4 *dst = reinterpret_cast<u32x4 *>(out + head);
+    for (int j = (int) threadIdx.x; j < cnt; j += 64 * K) {
+        Vec16<T> x[K], r;
+#pragma unroll
+        for (int k = 0; k < K; k++) x[k].v = read_shifted<T>(tile[k], j, sh[k]);
+        fold_vec<T, OP, K>(x, r);
+        __builtin_nontemporal_store(r.v, dst + base + j);
+    }
+}
+
 // Element-granular fallback for inputs whose 16-byte phases differ.
 template <typename T, int OP, int K>
 __global__ __launch_bounds__(kBlock) void combine_scalar_kernel(T *out, Inputs<T, K> in,
@@ -268,9 +378,83 @@ static hipError_t launch_k(T *out, const T *const *srcs, size_t n, hipStream_t s
     return launch((size_t) kBlock * U, kBlock, combine_vec_kernel<T, OP, K>);
 }
 
+// launch_combine_shifted's choice for one chunk: the kernels above when all
+// phases agree (and for one input, a copy, and for 16-byte elements, which
+// always share a phase), combine_shift_kernel when every pointer is aligned
+// to its element, combine_scalar_kernel (through launch_k) otherwise.
+// What launch_shift_k chose, per process (shift_route_counts; tests and
+// tools/rscatter_rate.py): chunks handed to launch_k's own choice, chunks on
+// combine_shift_kernel, chunks off their element alignment, and the
+// launches of combine_shift_kernel.
+static std::atomic<unsigned long long> g_shift_routes[4];
+
+template <typename T, int OP, int K>
+static hipError_t launch_shift_k(T *out, const T *const *srcs, size_t n, hipStream_t s)
+{
+    if constexpr (K < 2 || K > kCombineLdsMaxK || sizeof(T) >= 16) {
+        g_shift_routes[0]++;
+        return launch_k<T, OP, K>(out, srcs, n, s);
+    } else {
+        constexpr size_t E = sizeof(T);
+        constexpr size_t W = 16 / E;
+        bool same = true, elem = (uintptr_t) out % E == 0;
+        for (int k = 0; k < K; k++) {
+            same = same && (((uintptr_t) srcs[k] ^ (uintptr_t) out) & 15) == 0;
+            elem = elem && (uintptr_t) srcs[k] % E == 0;
+        }
+        if (same || !elem) {
+            g_shift_routes[elem ? 0 : 2]++;
+            return launch_k<T, OP, K>(out, srcs, n, s);
+        }
+        g_shift_routes[1]++;
+        // the split of the target alone; then the vector body gives up its
+        // first / last vector to the edges where an input's aligned vectors
+        // covering it would start before that input or end past it
+        const VecSplit vs = vec_split(E, n, &out, 1, srcs, 0);
+        size_t head = vs.head, nvec = vs.nvec;
+        const size_t tail_bytes = (n - vs.tail_start) * E;
+        bool cut_first = false, cut_last = false;
+        for (int k = 0; k < K; k++) {
+            const size_t sh = (uintptr_t) (srcs[k] + head) & 15;
+            cut_first = cut_first || (sh != 0 && head * E < sh);
+            cut_last = cut_last || (sh != 0 && tail_bytes < 16 - sh);
+        }
+        if (cut_first && nvec > 0) head += W, nvec--;
+        if (cut_last && nvec > 0) nvec--;
+        const size_t tail_start = head + nvec * W;
+        const int nedge = (int) (head + (n - tail_start));  // < 4 W <= 32 lanes
+        Inputs<T, K> in;
+        for (int k = 0; k < K; k++) in.p[k] = srcs[k];
+        constexpr size_t V = (size_t) 64 * OSGPU_SHIFT_U;
+        return for_each_tile_run(nvec, V, 64 * K, 1, [&](size_t t0, size_t nt, size_t nv) {
+            auto kernel = combine_shift_kernel<T, OP, K, OSGPU_SHIFT_U>;
+            g_shift_routes[3]++;
+            if (t0 == 0) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned) nt), dim3(64 * K), 0, s, out, in, nv, head,
+                                   tail_start, nedge);
+            } else {
+                // a later run: a non-last run's halo is the next run's first vector
+                const size_t off = head + t0 * V * W;
+                Inputs<T, K> ic;
+                for (int k = 0; k < K; k++) ic.p[k] = in.p[k] + off;
+                hipLaunchKernelGGL(kernel, dim3((unsigned) nt), dim3(64 * K), 0, s, out + off, ic, nv,
+                                   (size_t) 0, (size_t) 0, 0);
+            }
+            return hipGetLastError();
+        });
+    }
+}
+
 constexpr int kMaxK = 8;
 
-template <typename T, int OP>
+template <typename T, int OP, int K, bool SHIFT>
+static hipError_t launch_chunk(T *out, const T *const *srcs, size_t n, hipStream_t s)
+{
+    if constexpr (SHIFT) return launch_shift_k<T, OP, K>(out, srcs, n, s);
+    else return launch_k<T, OP, K>(out, srcs, n, s);
+}
+
+template <typename T, int OP, bool SHIFT = false>
 static hipError_t launch_op(void *out_, const void *const *srcs_, int k, size_t n,
                             hipStream_t s)
 {
@@ -286,14 +470,14 @@ static hipError_t launch_op(void *out_, const void *const *srcs_, int k, size_t 
         if (done > 0) chunk[m++] = out;
         while (m < kMaxK && done < k) chunk[m++] = srcs[done++];
         switch (m) {
-        case 1: err = launch_k<T, OP, 1>(out, chunk, n, s); break;
-        case 2: err = launch_k<T, OP, 2>(out, chunk, n, s); break;
-        case 3: err = launch_k<T, OP, 3>(out, chunk, n, s); break;
-        case 4: err = launch_k<T, OP, 4>(out, chunk, n, s); break;
-        case 5: err = launch_k<T, OP, 5>(out, chunk, n, s); break;
-        case 6: err = launch_k<T, OP, 6>(out, chunk, n, s); break;
-        case 7: err = launch_k<T, OP, 7>(out, chunk, n, s); break;
-        default: err = launch_k<T, OP, 8>(out, chunk, n, s); break;
+        case 1: err = launch_chunk<T, OP, 1, SHIFT>(out, chunk, n, s); break;
+        case 2: err = launch_chunk<T, OP, 2, SHIFT>(out, chunk, n, s); break;
+        case 3: err = launch_chunk<T, OP, 3, SHIFT>(out, chunk, n, s); break;
+        case 4: err = launch_chunk<T, OP, 4, SHIFT>(out, chunk, n, s); break;
+        case 5: err = launch_chunk<T, OP, 5, SHIFT>(out, chunk, n, s); break;
+        case 6: err = launch_chunk<T, OP, 6, SHIFT>(out, chunk, n, s); break;
+        case 7: err = launch_chunk<T, OP, 7, SHIFT>(out, chunk, n, s); break;
+        default: err = launch_chunk<T, OP, 8, SHIFT>(out, chunk, n, s); break;
         }
     }
     return err;
@@ -307,6 +491,25 @@ hipError_t launch_combine(int type, int op, void *out, const void *const *srcs, 
     if (type == T_LONGDOUBLE) return launch_longdouble(op, out, srcs, k, n, s);
     return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
         return launch_op<typename decltype(t)::type, decltype(o)::value>(out, srcs, k, n, s);
+    });
+}
+
+void shift_route_counts(unsigned long long out[4], int *u)
+{
+    for (int i = 0; i < 4; i++) out[i] = g_shift_routes[i].load();
+    *u = OSGPU_SHIFT_U;
+}
+
+// launch_combine with every pointer at its own 16-byte phase (the feedback of
+// `out` as input 0 of a second chunk is why every input has its own shift)
+hipError_t launch_combine_shifted(int type, int op, void *out, const void *const *srcs, int k,
+                                  size_t n, hipStream_t s)
+{
+    if (k < 1 || out == nullptr) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    if (type == T_LONGDOUBLE) return launch_longdouble(op, out, srcs, k, n, s);
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return launch_op<typename decltype(t)::type, decltype(o)::value, true>(out, srcs, k, n, s);
     });
 }
 

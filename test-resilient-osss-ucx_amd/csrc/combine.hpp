@@ -22,6 +22,20 @@ enum TypeCode {
 // peer GPU's HBM mapped into this process).  `out` may alias srcs[0].
 hipError_t launch_combine(int type, int op, void *out, const void *const *srcs, int k,
                           size_t n, hipStream_t s);
+// The same where the pointers' 16-byte phases may differ (the reduce-scatter:
+// block m of every source into a target at its own address): while every
+// pointer is aligned to its element, 2..8 inputs per chunk stream as aligned
+// 16-byte vectors through combine_shift_kernel (combine.hip); equal phases
+// take launch_combine's kernels, pointers off their element alignment the
+// element-granular one.
+hipError_t launch_combine_shifted(int type, int op, void *out, const void *const *srcs, int k,
+                                  size_t n, hipStream_t s);
+// Its choices so far in this process (osgpu_test_shift_routes): out[0] chunks
+// handed to launch_combine's kernels (equal phases, one input, 16-byte
+// elements), out[1] chunks on combine_shift_kernel, out[2] chunks with a
+// pointer off its element alignment (the element-granular kernel), out[3]
+// launches of combine_shift_kernel; *u: the build's OSGPU_SHIFT_U.
+void shift_route_counts(unsigned long long out[4], int *u);
 
 // Owner-computes team combine over an active set of P PEs (2 <= P <= 8):
 // for i < n, dsts[q][i] = fold of srcs[*][i] in PE q's order (q first, then

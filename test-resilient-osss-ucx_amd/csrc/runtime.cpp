@@ -1538,6 +1538,26 @@ int osgpu_combine(int type, int op, void *target, const void *const *srcs, int n
     return OSGPU_OK;
 }
 
+int osgpu_combine_shifted(int type, int op, void *target, const void *const *srcs, int nsrc,
+                          size_t nelems, void *hip_stream)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)) || nsrc < 1 || !target || !srcs) {
+        set_err("osgpu_combine_shifted: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_combine_shifted");
+    hipError_t e = osgpu::launch_combine_shifted(type, op, target, srcs, nsrc, nelems, st);
+    if (e == hipErrorNotSupported) {
+        set_err("osgpu_combine_shifted: type %d op %d not supported on the GPU", type, op);
+        return OSGPU_ENOTSUP;
+    }
+    if (e != hipSuccess) {
+        set_err("osgpu_combine_shifted: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
 int osgpu_team_combine(int type, int op, int P, void *const *dsts, const void *const *srcs,
                        size_t nelems, void *hip_stream)
 {
@@ -1625,6 +1645,21 @@ int osgpu_test_strided_shape(int form, int u, int nt)
         set_err("osgpu_test_strided_shape: form -1..2, u 2, 4 or 8 (<= 0: the shipped shape)");
         return OSGPU_EINVAL;
     }
+    return OSGPU_OK;
+}
+
+// Test hook: which kernels osgpu_combine_shifted's chunks took so far in this
+// process and the vectors per lane this library's shift kernel was built
+// with (combine.hpp shift_route_counts).  Results are bit-identical on every
+// route, so only this tells the shift kernel from a fall-back.
+int osgpu_test_shift_routes(unsigned long long counts[4], int *u)
+{
+    const char *on = getenv("OSGPU_TEST_HOOKS");
+    if (!on || strcmp(on, "1") || !counts || !u) {
+        set_err("osgpu_test_shift_routes: test hooks are off (OSGPU_TEST_HOOKS=1 enables them)");
+        return OSGPU_EINVAL;
+    }
+    osgpu::shift_route_counts(counts, u);
     return OSGPU_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "../../include/osgpu_reduce.h"
 #include "call_common.hpp"
 #include "combine.hpp"
+#include "rscatter_host.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -770,6 +771,170 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
     }
 }
 
+// ------------------------------------------------------- reduce-scatter
+//
+// osgpu_reduce_scatter: member m of the set receives block m -- elements
+// [m * nreduce, (m + 1) * nreduce) -- of what the reduce-to-all over the same
+// P * nreduce element sources would leave in its target, bit for bit: the
+// same fold order and element rules over a P-th of the elements.  `c.nbytes`
+// is the block's size; the byte arithmetic is rscatter_host.hpp's (size_t).
+// Paths: device heaps the pull form; host heaps the host fold and GETMEM.
+// No FUSED, STAGED, RCCL or owner-push form.
+
+// Device heaps, every member's registered: run_p2p over block m of every
+// member's source.  Block m starts m * nreduce * size bytes into a source and
+// the target sits at its own address, so the pointers' 16-byte phases differ
+// unless the block is a multiple of 16 bytes: launch_combine_shifted.
+void run_rs_pull(const Call &c, const RsBlock &b)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size;
+    int seg = -1;
+    size_t off = 0;
+    bool ok = heap_locate(c.me, c.source, b.source_bytes, &seg, &off);
+    std::vector<int> order(P);
+    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    std::vector<const void *> srcs(P);  // block m of every source, in this PE's fold order
+    for (int k = 0; ok && k < P; k++) {
+        char *p = nullptr;
+        ok = heap_peer(order[k], seg, off, b.source_bytes, &p);
+        srcs[k] = ok ? p + b.offset : nullptr;
+    }
+    if (!ok)
+        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
+                      "(osgpu_heap_create / osgpu_heap_register) and the whole %zu-byte source "
+                      "inside it", b.source_bytes);
+    t_last_path = OSGPU_RAN_PULL;
+    DBG("%s PE %d: pull path, block %d of %d, %zu bytes at %zu", c.name, c.me, c.index_of(c.me), P,
+        b.bytes, b.offset);
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready
+    const bool overlap = P > 1 && ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
+    const DeviceOut out(c, c.target, overlap, b.bytes);
+    launched(c.name, "combine launch",
+             osgpu::launch_combine_shifted(c.type, c.op, out.out, srcs.data(), P,
+                                           (size_t) c.nreduce, st));
+    stream_wait(c.name, st);
+    barrier(c);  // peers are done reading my source
+    out.finish(b.bytes, st);
+}
+
+// Host heaps, what the caller pulls ((P - 1) blocks) at most
+// host_fold_max_bytes(): run_host_fold over block m, one shmem_getmem of the
+// block per peer.  No peer, no peer buffer.
+void run_rs_host_fold(const Call &c, const RsBlock &b)
+{
+    t_last_path = OSGPU_RAN_HOST_FOLD;
+    const int P = c.PE_size;
+    std::vector<int> order(P);
+    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    const bool overlap = ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
+    thread_local std::vector<unsigned char> tmp, peer;
+    if (overlap) tmp.resize(b.bytes);
+    if (P > 1) peer.resize(b.bytes);
+    void *acc = overlap ? (void *) tmp.data() : c.target;
+    const bool ok = rs_host_fold(
+        b, c.source, acc, P > 1 ? peer.data() : nullptr, order.data(), P, (size_t) c.nreduce,
+        [&](void *dst, const void *src, size_t n, int pe) { c.ops.getmem(dst, src, n, pe); },
+        [&](void *a, const void *in, size_t n) { return osgpu::host_fold(c.type, c.op, a, in, n); },
+        [&] {
+            // long double at P == 1: zero padding, as run_host_fold
+            if (c.type == osgpu::T_LONGDOUBLE && P == 1)
+                for (size_t i = 0; i < (size_t) c.nreduce; i++)
+                    memset((char *) acc + 16 * i + 10, 0, 6);
+            barrier(c);  // every source is ready
+        });
+    if (!ok) fatal(c.name, "host fold: type %d op %d", c.type, c.op);
+    barrier(c);  // every peer is done reading my source
+    if (overlap) memcpy(c.target, acc, b.bytes);
+}
+
+// Host heaps above that: run_host restricted to block m, in chunks of
+// host_chunk_bytes().
+void run_rs_host(const Call &c, const RsBlock &b)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
+    const int P = c.PE_size;
+    t_last_path = OSGPU_RAN_GETMEM;
+    std::vector<int> order(P);
+    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    const size_t chunk = rs_chunk_elems(host_chunk_bytes(), s, N), cb = chunk * s;
+    char *dbuf = (char *) device_scratch(c.name, c.me, cb * (P + 1));
+    char *hbuf = (char *) host_stage(c.name, c.me, cb * (P + 1));
+    const bool overlap = P > 1 && ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
+    HostTmp result(c, c.target, overlap, b.bytes);
+    std::vector<const void *> srcs(P);
+    for (int k = 0; k < P; k++) srcs[k] = dbuf + (size_t) k * cb;
+    const char *mine = (const char *) c.source + b.offset;
+
+    barrier(c);  // every source is ready
+    for (size_t off = 0; off < N; off += chunk) {
+        const size_t n = N - off < chunk ? N - off : chunk, nb = n * s;
+        for (int k = 0; k < P; k++) {
+            char *hk = hbuf + (size_t) k * cb;
+            if (order[k] == c.me) memcpy(hk, mine + off * s, nb);
+            else c.ops.getmem(hk, mine + off * s, nb, order[k]);
+            HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
+        }
+        // (a slot of cb bytes need not be a multiple of 16: the slots' phases may differ)
+        char *dout = dbuf + (size_t) P * cb, *hout = hbuf + (size_t) P * cb;
+        launched(c.name, "combine launch",
+                 osgpu::launch_combine_shifted(c.type, c.op, dout, srcs.data(), P, n, st));
+        HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
+        stream_wait(c.name, st);
+        memcpy(result.out + off * s, hout, nb);
+    }
+    barrier(c);  // every peer is done reading my source
+    result.finish(b.bytes);
+}
+
+void reduce_scatter(const char *name, int type, int op, void *target, const void *source,
+                    int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)))
+        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_scatter)",
+              type, op);
+    Call c;
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    c.target = target;
+    c.source = const_cast<void *>(source);
+    c.nreduce = nreduce;
+    if (nreduce <= 0) {  // nothing to combine; the collective still syncs
+        t_last_path = OSGPU_RAN_BARRIER_ONLY;
+        sync_only(c);
+        return;
+    }
+    RsBlock b;
+    if (!rs_block(type_size(type), nreduce, PE_size, c.index_of(c.me), &b))
+        fatal(name, "%d blocks of %d elements do not fit the address space", PE_size, nreduce);
+    c.nbytes = b.bytes;
+
+    int dt = -1, ds = -1;
+    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
+    if (kt != ks)
+        fatal(name, "target and source must both be device or both be host memory");
+    if (kt == MEM_HOST) {
+        const int hp = host_path();
+        require_host_heaps(c);
+        // a size every member shares: all of them take the same path
+        const size_t fold_lim = host_fold_max_bytes();  // 0: off
+        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bytes <= fold_lim &&
+            osgpu::host_fold_supported(type, op)) {
+            run_rs_host_fold(c, b);
+            return;
+        }
+        if (hp == OSGPU_HOST_STAGED)
+            DBG("%s PE %d: no STAGED form of the reduce-scatter, taking GETMEM", name, c.me);
+        run_rs_host(c, b);
+        return;
+    }
+    const DeviceGuard on_device(name, dt);
+    run_rs_pull(c, b);  // under every OSGPU_REDUCE_PATH setting; RCCL never serves it
+}
+
 }  // namespace
 
 extern "C" int osgpu_last_path(void) { return t_last_path; }
@@ -864,4 +1029,22 @@ extern "C" void osgpu_reduce_ext(int type, int op, void *target, const void *sou
                          type, op, (int) OSGPU_T_HALF, (int) OSGPU_T_BFLOAT16);
     to_all("osgpu_reduce_ext", type, op, target, const_cast<void *>(source), nreduce, PE_start,
            logPE_stride, PE_size, pWrk, pSync);
+}
+
+// ======================================================================
+// Part 1d: reduce-scatter (no reference counterpart: osgpu_* names only)
+// ======================================================================
+
+extern "C" void osgpu_reduce_scatter(int type, int op, void *target, const void *source,
+                                     int nreduce, int PE_start, int logPE_stride, int PE_size,
+                                     void *pWrk, long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    reduce_scatter("osgpu_reduce_scatter", type, op, target, source, nreduce, PE_start,
+                   logPE_stride, PE_size, pSync);
+}
+
+extern "C" int osgpu_has_reduce_scatter(int type, int op)
+{
+    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
 }

@@ -153,6 +153,10 @@ def load() -> ctypes.CDLL:
     L.osgpu_set_stream.argtypes = [vp]
     L.osgpu_get_stream.restype = vp
     L.osgpu_combine.argtypes = [i, i, vp, vp, i, sz, vp]
+    L.osgpu_combine_shifted.argtypes = [i, i, vp, vp, i, sz, vp]
+    L.osgpu_reduce_scatter.argtypes = [i, i, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_reduce_scatter.restype = None
+    L.osgpu_has_reduce_scatter.argtypes = [i, i]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -355,6 +359,26 @@ def combine(t: str, op: str, target: int, srcs, n: int, stream: int | None = Non
     if rc != 0:
         raise RuntimeError(f"osgpu_combine({t},{op}) = {rc}: "
                            f"{L.osgpu_last_error().decode()}")
+
+
+def combine_shifted(t: str, op: str, target: int, srcs, n: int, stream: int | None = None):
+    """Enqueue osgpu_combine_shifted: combine() for pointers whose 16-byte
+    phases differ (device ptrs)."""
+    L = load()
+    arr = (ctypes.c_void_p * len(srcs))(*srcs)
+    rc = L.osgpu_combine_shifted(type_code(t), OPS.index(op), target, arr, len(srcs), n, stream)
+    if rc != 0:
+        raise RuntimeError(f"osgpu_combine_shifted({t},{op}) = {rc}: "
+                           f"{L.osgpu_last_error().decode()}")
+
+
+def reduce_scatter(t: str, op: str):
+    """osgpu_reduce_scatter bound to the codes of (t, op): a function with the
+    arguments of shmem_<t>_<op>_to_all (target, source, nreduce, PE_start,
+    logPE_stride, PE_size, pWrk, pSync), nreduce the elements each member
+    receives of a source of PE_size * nreduce."""
+    f, tc, oc = load().osgpu_reduce_scatter, type_code(t), OPS.index(op)
+    return lambda *args: f(tc, oc, *args)
 
 
 def copy(dsts, srcs, nbytes, stream: int | None = None):
