@@ -24,7 +24,10 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <vector>
+
 #include "kernel_common.hpp"
+#include "many_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -321,6 +324,81 @@ __global__ __launch_bounds__(64 * K) void combine_shift_kernel(T *out, Inputs<T,
     }
 }
 
+// Batched form of combine_lds_kernel (launch_combine_many): one grid over a
+// table of up to kManySegs independent arrays, each a segment with its own
+// pointers, vector split and run of workgroups.  The table travels by value
+// in the kernel arguments (K = 8: 104 bytes a segment, 1664 in all), so no
+// copy to the device sits on the latency path.  A workgroup finds its segment
+// by counting the segments that start at or before it (unused ones start at
+// ~0u); the index is wave-uniform and kept in an SGPR, so the segment's
+// fields -- wave k's input pointer among them -- are scalar loads from the
+// kernel argument segment.  Within the segment the workgroup is
+// combine_lds_kernel's: wave k streams input k's tile, the tile is folded in
+// input order, the segment's first workgroup folds its edges.
+// U = 2 (V = 128 vectors), the shift kernel's shape: not measured against
+// U = 1 and 4.
+#ifndef OSGPU_MANY_U
+#define OSGPU_MANY_U 2  // vectors per lane per input, every K
+#endif
+
+template <typename T, int K>
+struct ManySeg {
+    T *out;
+    const T *in[K];
+    size_t nvec, head, tail_start;
+    int nedge;
+    unsigned first;  // the segment's first workgroup of the launch
+};
+
+template <typename T, int K>
+struct ManyTable {
+    ManySeg<T, K> seg[kManySegs];
+};
+
+template <typename T, int OP, int K, int U>
+__global__ __launch_bounds__(64 * K) void combine_many_kernel(ManyTable<T, K> tab)
+{
+    constexpr int V = 64 * U;  // vectors per input per tile
+    __shared__ u32x4 tile[K][V];
+    int si = 0;
+#pragma unroll
+    for (int i = 1; i < kManySegs; i++) si += blockIdx.x >= tab.seg[i].first ? 1 : 0;
+    si = __builtin_amdgcn_readfirstlane(si);
+    const ManySeg<T, K> &g = tab.seg[si];
+    const unsigned blk = blockIdx.x - g.first;
+    T *out = g.out;
+    const size_t nvec = g.nvec, head = g.head;
+    if (blk == 0 && (int) threadIdx.x < g.nedge) {
+        Inputs<T, K> in;
+#pragma unroll
+        for (int k = 0; k < K; k++) in.p[k] = g.in[k];
+        const size_t e = edge_index(head, g.tail_start);
+        out[e] = fold_scalar<T, OP, K>(in, e);
+    }
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63);
+    const size_t base = (size_t) blk * V;
+    const bool whole = base + V <= nvec;
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(g.in[w] + head);
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++)
+        if (whole || base + u * 64 + lane < nvec)
+            v[u] = __builtin_nontemporal_load(src + base + u * 64 + lane);
+#pragma unroll
+    for (int u = 0; u < U; u++) tile[w][u * 64 + lane] = v[u];
+    __syncthreads();
+    u32x4 *dst = reinterpret_cast<u32x4 *>(out + head);
+    for (int j = (int) threadIdx.x; j < V; j += 64 * K) {
+        if (!whole && base + j >= nvec) continue;
+        Vec16<T> x[K], r;
+#pragma unroll
+        for (int k = 0; k < K; k++) x[k].v = tile[k][j];
+        fold_vec<T, OP, K>(x, r);
+        __builtin_nontemporal_store(r.v, dst + base + j);
+    }
+}
+
 // Element-granular fallback for inputs whose 16-byte phases differ.
 template <typename T, int OP, int K>
 __global__ __launch_bounds__(kBlock) void combine_scalar_kernel(T *out, Inputs<T, K> in,
@@ -511,6 +589,137 @@ hipError_t launch_combine_shifted(int type, int op, void *out, const void *const
     return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
         return launch_op<typename decltype(t)::type, decltype(o)::value, true>(out, srcs, k, n, s);
     });
+}
+
+// ------------------------------------------------------- batched combine
+// What launch_combine_many chose, per process (many_route_counts): [0]
+// segments on combine_many_kernel (continuations included), entries sent to
+// [1] launch_combine_shifted, [2] launch_longdouble, [3] launch_combine's
+// chunks of 8, [4] the one-input copy, [5] launches of combine_many_kernel,
+// [6] continuations (segments that carry on an entry split between launches).
+static std::atomic<unsigned long long> g_many_routes[7];
+
+// one launch: the pieces' segments of the table, `blocks` workgroups
+template <typename T, int OP, int K>
+static hipError_t launch_many_k(const rt::ManyPiece *pc, int np, size_t blocks,
+                                void *const *targets, const void *const *const *srcs,
+                                const size_t *nelems, hipStream_t s)
+{
+    constexpr size_t W = 16 / sizeof(T), V = (size_t) 64 * OSGPU_MANY_U;
+    ManyTable<T, K> tab;
+    for (int i = 0; i < kManySegs; i++) {
+        tab.seg[i] = ManySeg<T, K>{};
+        tab.seg[i].first = ~0u;
+    }
+    for (int i = 0; i < np; i++) {
+        const int e = pc[i].entry;
+        T *out = static_cast<T *>(targets[e]);
+        const T *const *in = reinterpret_cast<const T *const *>(srcs[e]);
+        const VecSplit vs = vec_split(sizeof(T), nelems[e], &out, 1, in, K);
+        if (!vs.vec) return hipErrorInvalidValue;  // many_route said MANY_BATCH
+        ManySeg<T, K> &g = tab.seg[i];
+        const size_t t0 = pc[i].tile0;
+        const size_t left = vs.nvec > t0 * V ? vs.nvec - t0 * V : 0;
+        g.nvec = left < pc[i].ntiles * V ? left : pc[i].ntiles * V;
+        g.first = pc[i].first;
+        if (t0 == 0) {
+            g.out = out;
+            for (int k = 0; k < K; k++) g.in[k] = in[k];
+            g.head = vs.head;
+            g.tail_start = vs.tail_start;
+            g.nedge = vs.nedge;
+        } else {
+            // a continuation: no edges, pointers at its first tile (for_each_tile_run's rule)
+            const size_t off = vs.head + t0 * V * W;
+            g.out = out + off;
+            for (int k = 0; k < K; k++) g.in[k] = in[k] + off;
+            g_many_routes[6]++;
+        }
+    }
+    g_many_routes[0] += (unsigned long long) np;
+    g_many_routes[5]++;
+    hipLaunchKernelGGL((combine_many_kernel<T, OP, K, OSGPU_MANY_U>), dim3((unsigned) blocks),
+                       dim3(64 * K), 0, s, tab);
+    return hipGetLastError();
+}
+
+template <typename T, int OP>
+static hipError_t launch_many_op(int count, void *const *targets, const void *const *const *srcs,
+                                 int nsrc, const size_t *nelems, hipStream_t s)
+{
+    constexpr size_t V = (size_t) 64 * OSGPU_MANY_U;
+    // entries of the batch kernel: their workgroups; the others are launched
+    // here, each on its own (independent arrays: the order is free)
+    std::vector<size_t> tiles((size_t) count, 0);
+    std::vector<uintptr_t> at((size_t) nsrc);
+    for (int i = 0; i < count; i++) {
+        if (nelems[i] == 0) continue;
+        if (!targets[i] || !srcs[i]) return hipErrorInvalidValue;
+        for (int k = 0; k < nsrc; k++) at[(size_t) k] = (uintptr_t) srcs[i][k];
+        const rt::ManyRoute r = rt::many_route(sizeof(T), false, nsrc, nelems[i],
+                                               (uintptr_t) targets[i], at.data());
+        hipError_t e = hipSuccess;
+        if (r == rt::MANY_BATCH) {
+            T *out = static_cast<T *>(targets[i]);
+            const VecSplit vs = vec_split(sizeof(T), nelems[i], &out, 1,
+                                          reinterpret_cast<const T *const *>(srcs[i]), nsrc);
+            tiles[(size_t) i] = rt::many_tiles(vs.nvec, V);
+        } else if (r == rt::MANY_SHIFTED) {
+            g_many_routes[1]++;
+            e = launch_op<T, OP, true>(targets[i], srcs[i], nsrc, nelems[i], s);
+        } else {
+            g_many_routes[r == rt::MANY_COPY ? 4 : 3]++;
+            e = launch_op<T, OP>(targets[i], srcs[i], nsrc, nelems[i], s);
+        }
+        if (e != hipSuccess) return e;
+    }
+    if (nsrc < 2 || nsrc > kMaxK) return hipSuccess;
+    hipError_t err = hipSuccess;
+    auto pack = [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        rt::many_pack(tiles.data(), count, max_launch_threads() / (64 * K),
+                      [&](const rt::ManyPiece *pc, int np, size_t blocks) {
+                          err = launch_many_k<T, OP, K>(pc, np, blocks, targets, srcs, nelems, s);
+                          return err == hipSuccess;
+                      });
+    };
+    switch (nsrc) {
+    case 2: pack(std::integral_constant<int, 2>{}); break;
+    case 3: pack(std::integral_constant<int, 3>{}); break;
+    case 4: pack(std::integral_constant<int, 4>{}); break;
+    case 5: pack(std::integral_constant<int, 5>{}); break;
+    case 6: pack(std::integral_constant<int, 6>{}); break;
+    case 7: pack(std::integral_constant<int, 7>{}); break;
+    default: pack(std::integral_constant<int, 8>{}); break;
+    }
+    return err;
+}
+
+hipError_t launch_combine_many(int type, int op, int count, void *const *targets,
+                               const void *const *const *srcs, int nsrc, const size_t *nelems,
+                               hipStream_t s)
+{
+    if (count < 0 || nsrc < 1 || (count > 0 && (!targets || !srcs || !nelems)))
+        return hipErrorInvalidValue;
+    if (type == T_LONGDOUBLE) {
+        for (int i = 0; i < count; i++) {
+            if (nelems[i] == 0) continue;
+            if (!targets[i] || !srcs[i]) return hipErrorInvalidValue;
+            g_many_routes[2]++;
+            const hipError_t e = launch_longdouble(op, targets[i], srcs[i], nsrc, nelems[i], s);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return launch_many_op<typename decltype(t)::type, decltype(o)::value>(count, targets, srcs,
+                                                                              nsrc, nelems, s);
+    });
+}
+
+void many_route_counts(unsigned long long out[7])
+{
+    for (int i = 0; i < 7; i++) out[i] = g_many_routes[i].load();
 }
 
 }  // namespace osgpu

@@ -36,6 +36,26 @@ hipError_t launch_combine_shifted(int type, int op, void *out, const void *const
 // pointer off its element alignment (the element-granular kernel), out[3]
 // launches of combine_shift_kernel; *u: the build's OSGPU_SHIFT_U.
 void shift_route_counts(unsigned long long out[4], int *u);
+// launch_combine over a table of `count` independent arrays (the batched
+// reduce-to-all): targets[i] = fold of srcs[i][0 .. nsrc) over nelems[i]
+// elements, empty entries skipped.  An entry of 2..8 inputs whose pointers
+// share one 16-byte phase (entries may differ from each other) becomes a
+// segment of combine_many_kernel (combine.hip), up to kManySegs
+// (many_host.hpp) segments and max_launch_threads() threads a launch, an
+// entry that does not fit split at a tile boundary; any other entry is
+// launched on its own on the same stream -- launch_combine_shifted for a
+// phase mismatch or a pointer off its element, launch_longdouble, and
+// launch_combine for more than 8 inputs or one.  The host tables are read
+// before the call returns.
+hipError_t launch_combine_many(int type, int op, int count, void *const *targets,
+                               const void *const *const *srcs, int nsrc, const size_t *nelems,
+                               hipStream_t s);
+// Its choices so far in this process (osgpu_test_many_routes): out[0]
+// segments on combine_many_kernel (continuations included), entries sent to
+// out[1] launch_combine_shifted, out[2] launch_longdouble, out[3]
+// launch_combine's chunks of 8, out[4] the one-input copy, out[5] launches of
+// combine_many_kernel, out[6] continuations of entries split between launches.
+void many_route_counts(unsigned long long out[7]);
 
 // Owner-computes team combine over an active set of P PEs (2 <= P <= 8):
 // for i < n, dsts[q][i] = fold of srcs[*][i] in PE q's order (q first, then

@@ -1558,6 +1558,30 @@ int osgpu_combine_shifted(int type, int op, void *target, const void *const *src
     return OSGPU_OK;
 }
 
+int osgpu_combine_many(int type, int op, int count, void *const *targets,
+                       const void *const *const *srcs, int nsrc, const size_t *nelems,
+                       void *hip_stream)
+{
+    bool ok = (has_op(type, op) || has_ext_op(type, op)) && nsrc >= 1 && count >= 0 &&
+              (count == 0 || (targets && srcs && nelems));
+    for (int i = 0; ok && i < count; i++) ok = nelems[i] == 0 || (targets[i] && srcs[i]);
+    if (!ok) {
+        set_err("osgpu_combine_many: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_combine_many");
+    hipError_t e = osgpu::launch_combine_many(type, op, count, targets, srcs, nsrc, nelems, st);
+    if (e == hipErrorNotSupported) {
+        set_err("osgpu_combine_many: type %d op %d not supported on the GPU", type, op);
+        return OSGPU_ENOTSUP;
+    }
+    if (e != hipSuccess) {
+        set_err("osgpu_combine_many: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
 int osgpu_team_combine(int type, int op, int P, void *const *dsts, const void *const *srcs,
                        size_t nelems, void *hip_stream)
 {
@@ -1660,6 +1684,22 @@ int osgpu_test_shift_routes(unsigned long long counts[4], int *u)
         return OSGPU_EINVAL;
     }
     osgpu::shift_route_counts(counts, u);
+    return OSGPU_OK;
+}
+
+// Test hook: what osgpu_combine_many's launcher chose so far in this process
+// (combine.hpp many_route_counts): segments on the batch kernel, entries sent
+// to each fall-back (shifted, long double, chunks of 8, one-input copy),
+// launches of the batch kernel, continuations of split entries.  Every route
+// gives the same bits, so only this tells the batch kernel from a fall-back.
+int osgpu_test_many_routes(unsigned long long counts[7])
+{
+    const char *on = getenv("OSGPU_TEST_HOOKS");
+    if (!on || strcmp(on, "1") || !counts) {
+        set_err("osgpu_test_many_routes: test hooks are off (OSGPU_TEST_HOOKS=1 enables them)");
+        return OSGPU_EINVAL;
+    }
+    osgpu::many_route_counts(counts);
     return OSGPU_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "../../include/osgpu_reduce.h"
 #include "call_common.hpp"
 #include "combine.hpp"
+#include "many_host.hpp"
 #include "rscatter_host.hpp"
 #include "runtime.hpp"
 
@@ -595,12 +596,13 @@ void run_staged(const Call &c, StageSet &S)
 // memory (the UCX heap).  Peers' sources are pulled with the runtime's
 // shmem_getmem (src/putget.h:539-561), like the reference, but in large
 // chunks into pinned staging, then combined on the GPU.
-void run_host(const Call &c)
+// The chunk loop between the two barriers: c's fold into `result` (the
+// target or its temporary).  Also run once per entry by run_many_host.
+void host_chunks(const Call &c, char *result)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
     const int P = c.PE_size;
-    t_last_path = OSGPU_RAN_GETMEM;
     std::vector<int> order(P);
     fold_order(c.me, c.PE_start, c.step, P, order.data());
 
@@ -612,12 +614,9 @@ void run_host(const Call &c)
     // device: P input slots + 1 output slot; pinned: P input slots + output
     char *dbuf = (char *) device_scratch(c.name, c.me, cb * (P + 1));
     char *hbuf = (char *) host_stage(c.name, c.me, cb * (P + 1));
-    const bool overlap = P > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
-    HostTmp result(c, c.target, overlap, c.nbytes);
     std::vector<const void *> srcs(P);
     for (int k = 0; k < P; k++) srcs[k] = dbuf + (size_t) k * cb;
 
-    barrier(c);  // src/reductions.c:82
     for (size_t off = 0; off < (size_t) c.nreduce; off += chunk) {
         const size_t n = ((size_t) c.nreduce - off) < chunk ? ((size_t) c.nreduce - off) : chunk;
         const size_t nb = n * s;
@@ -634,8 +633,17 @@ void run_host(const Call &c)
         char *hout = hbuf + (size_t) P * cb;
         HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
         stream_wait(c.name, st);
-        memcpy(result.out + off * s, hout, nb);
+        memcpy(result + off * s, hout, nb);
     }
+}
+
+void run_host(const Call &c)
+{
+    t_last_path = OSGPU_RAN_GETMEM;
+    const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    HostTmp result(c, c.target, overlap, c.nbytes);
+    barrier(c);  // src/reductions.c:82
+    host_chunks(c, result.out);
     barrier(c);  // src/reductions.c:113
     result.finish(c.nbytes);  // src/reductions.c:114-119
 }
@@ -935,6 +943,212 @@ void reduce_scatter(const char *name, int type, int op, void *target, const void
     run_rs_pull(c, b);  // under every OSGPU_REDUCE_PATH setting; RCCL never serves it
 }
 
+// ------------------------------------------------- batched reduce-to-all
+//
+// osgpu_reduce_many: a table of independent reduce-to-all calls of one type,
+// op and active set between ONE pair of barriers.  Every targets[i] ends up,
+// bit for bit, as the single call on (targets[i], sources[i], nreduces[i])
+// would leave it.  Paths: device heaps the pull form with one
+// launch_combine_many; host heaps the host fold and GETMEM.  No TEAM, FUSED,
+// STAGED or RCCL form, one type and op per call.
+
+// the non-empty entries of the table; c (a Call) carries set, type and op
+struct Many {
+    std::vector<void *> target;
+    std::vector<const void *> source;
+    std::vector<size_t> n, bytes;
+    size_t total = 0;  // bytes over all entries
+    int count() const { return (int) target.size(); }
+};
+
+// Where entry i's result goes while peers may still read what its target
+// overlaps: one temporary region for the whole table, each slot at its
+// target's 16-byte phase (the batch kernel wants target and sources at one
+// phase).  off[i] == (size_t) -1: the target itself.
+struct ManyTmp {
+    std::vector<size_t> off;
+    size_t bytes = 0;
+    // peers: somebody else reads the sources (or the path copies its own first)
+    ManyTmp(const Many &m, bool peers) : off((size_t) m.count(), (size_t) -1)
+    {
+        for (int i = 0; i < m.count(); i++) {
+            if (!peers || !ranges_overlap(m.target[i], m.bytes[i], m.source[i], m.bytes[i]))
+                continue;
+            off[i] = bytes + ((uintptr_t) m.target[i] & 15);
+            bytes = (off[i] + m.bytes[i] + 15) & ~(size_t) 15;
+        }
+    }
+    bool used(int i) const { return off[i] != (size_t) -1; }
+};
+
+void run_many_pull(const Call &c, const Many &m)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size, M = m.count();
+    std::vector<int> order(P);
+    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    // every entry's source on every member, in this PE's fold order
+    std::vector<const void *> srcs((size_t) M * P);
+    std::vector<const void *const *> rows(M);
+    for (int i = 0; i < M; i++) {
+        int seg = -1;
+        size_t off = 0;
+        bool ok = heap_locate(c.me, m.source[i], m.bytes[i], &seg, &off);
+        for (int k = 0; ok && k < P; k++) {
+            char *p = nullptr;
+            ok = heap_peer(order[k], seg, off, m.bytes[i], &p);
+            srcs[(size_t) i * P + k] = p;
+        }
+        if (!ok)
+            fatal(c.name, "device-resident arguments need every active PE's device heap registered "
+                          "(osgpu_heap_create / osgpu_heap_register) and every source inside it "
+                          "(entry %d of the non-empty ones, %zu bytes)", i, m.bytes[i]);
+        rows[i] = &srcs[(size_t) i * P];
+    }
+    t_last_path = OSGPU_RAN_PULL;
+    DBG("%s PE %d: pull path, %d arrays, %zu bytes", c.name, c.me, M, m.total);
+    entry_sync(c.name, st);
+    barrier(c);  // every source of every entry is ready
+    const ManyTmp tmp(m, P > 1);
+    char *scratch = tmp.bytes ? (char *) device_scratch(c.name, c.me, tmp.bytes) : nullptr;
+    std::vector<void *> outs(M);
+    for (int i = 0; i < M; i++) outs[i] = tmp.used(i) ? scratch + tmp.off[i] : m.target[i];
+    launched(c.name, "combine launch",
+             osgpu::launch_combine_many(c.type, c.op, M, outs.data(), rows.data(), P, m.n.data(),
+                                        st));
+    stream_wait(c.name, st);
+    barrier(c);  // peers are done reading my sources
+    if (tmp.bytes) {
+        std::vector<osgpu::CopySeg> segs;
+        for (int i = 0; i < M; i++)
+            if (tmp.used(i)) segs.push_back({outs[i], m.target[i], m.bytes[i]});
+        for_batches(segs, osgpu::kMaxCopySegs, [&](const osgpu::CopySeg *b, int k) {
+            launched(c.name, "copy launch", osgpu::launch_copy(b, k, st));
+        });
+        stream_wait(c.name, st);
+    }
+}
+
+void run_many_host_fold(const Call &c, const Many &m)
+{
+    t_last_path = OSGPU_RAN_HOST_FOLD;
+    const int P = c.PE_size, M = m.count();
+    std::vector<int> order(P);
+    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    // (the host fold copies its own source first, so any overlap takes a temporary, as run_host_fold)
+    const ManyTmp tmp(m, true);
+    thread_local std::vector<unsigned char> tbuf, peer;
+    tbuf.resize(tmp.bytes);
+    if (P > 1) peer.resize(*std::max_element(m.bytes.begin(), m.bytes.end()));
+    std::vector<void *> accs(M);
+    for (int i = 0; i < M; i++) accs[i] = tmp.used(i) ? (void *) (tbuf.data() + tmp.off[i]) : m.target[i];
+    const bool ok = many_host_fold(
+        M, accs.data(), m.source.data(), m.bytes.data(), m.n.data(), P > 1 ? peer.data() : nullptr,
+        order.data(), P,
+        [&](void *dst, const void *src, size_t n, int pe) { c.ops.getmem(dst, src, n, pe); },
+        [&](void *a, const void *in, size_t n, int) { return osgpu::host_fold(c.type, c.op, a, in, n); },
+        [&] {
+            // long double at P == 1: zero padding, as run_host_fold
+            if (c.type == osgpu::T_LONGDOUBLE && P == 1)
+                for (int i = 0; i < M; i++)
+                    for (size_t k = 0; k < m.n[i]; k++) memset((char *) accs[i] + 16 * k + 10, 0, 6);
+            barrier(c);  // every source is ready
+        });
+    if (!ok) fatal(c.name, "host fold: type %d op %d", c.type, c.op);
+    barrier(c);  // every peer is done reading my sources
+    for (int i = 0; i < M; i++)
+        if (tmp.used(i)) memcpy(m.target[i], accs[i], m.bytes[i]);
+}
+
+void run_many_host(const Call &c, const Many &m)
+{
+    t_last_path = OSGPU_RAN_GETMEM;
+    const int M = m.count();
+    const ManyTmp tmp(m, c.PE_size > 1);
+    std::vector<unsigned char> tbuf(tmp.bytes);
+    barrier(c);  // every source is ready
+    for (int i = 0; i < M; i++) {
+        Call e = c;
+        e.target = m.target[i];
+        e.source = const_cast<void *>(m.source[i]);
+        e.nreduce = (int) m.n[i];
+        e.nbytes = m.bytes[i];
+        host_chunks(e, tmp.used(i) ? (char *) tbuf.data() + tmp.off[i] : (char *) m.target[i]);
+    }
+    barrier(c);  // every peer is done reading my sources
+    for (int i = 0; i < M; i++)
+        if (tmp.used(i)) memcpy(m.target[i], tbuf.data() + tmp.off[i], m.bytes[i]);
+}
+
+void reduce_many(const char *name, int type, int op, int count, void *const *targets,
+                 const void *const *sources, const int *nreduces, int PE_start, int logPE_stride,
+                 int PE_size, long *pSync)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)))
+        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_many)", type,
+              op);
+    if (count < 0) fatal(name, "count %d is negative", count);
+    if (count > 0 && (!targets || !sources || !nreduces))
+        fatal(name, "a table of %d entries needs targets, sources and nreduces", count);
+    Call c;
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    Many m;
+    const size_t s = type_size(type);
+    for (int i = 0; i < count; i++) {
+        if (nreduces[i] <= 0) continue;
+        m.target.push_back(targets[i]);
+        m.source.push_back(sources[i]);
+        m.n.push_back((size_t) nreduces[i]);
+        m.bytes.push_back(s * (size_t) nreduces[i]);
+        m.total += m.bytes.back();
+    }
+    const int M = m.count();
+    if (M == 0) {  // nothing to combine; the collective still syncs
+        t_last_path = OSGPU_RAN_BARRIER_ONLY;
+        sync_only(c);
+        return;
+    }
+    {   // the table's contract, before the first barrier
+        std::vector<uintptr_t> ta(M), sa(M);
+        for (int i = 0; i < M; i++) ta[i] = (uintptr_t) m.target[i], sa[i] = (uintptr_t) m.source[i];
+        int other = -1;
+        const int bad = many_overlap(M, ta.data(), sa.data(), m.bytes.data(), &other);
+        if (bad >= 0)
+            fatal(name, "the target of one entry overlaps the target or source of another "
+                        "(non-empty entries %d and %d)", bad, other);
+    }
+    int dev = -1;
+    const MemKind kind = mem_kind(m.target[0], &dev);
+    // (an array inside my registered device heap needs no pointer query)
+    auto kind_of = [&](const void *p, size_t n) {
+        int seg = -1;
+        size_t off = 0;
+        return heap_locate(c.me, p, n, &seg, &off) ? MEM_DEVICE : mem_kind(p, nullptr);
+    };
+    for (int i = 0; i < M; i++)
+        if (kind_of(m.source[i], m.bytes[i]) != kind || (i && kind_of(m.target[i], m.bytes[i]) != kind))
+            fatal(name, "every target and source must be device memory, or every one host memory");
+    if (kind == MEM_HOST) {
+        const int hp = host_path();
+        require_host_heaps(c);
+        // a size every member shares: all of them take the same path
+        const size_t fold_lim = host_fold_max_bytes();  // 0: off
+        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && (size_t) (c.PE_size - 1) * m.total <= fold_lim &&
+            osgpu::host_fold_supported(type, op)) {
+            run_many_host_fold(c, m);
+            return;
+        }
+        if (hp == OSGPU_HOST_STAGED)
+            DBG("%s PE %d: no STAGED form of the batched reduce, taking GETMEM", name, c.me);
+        run_many_host(c, m);
+        return;
+    }
+    const DeviceGuard on_device(name, dev);
+    run_many_pull(c, m);  // under every OSGPU_REDUCE_PATH setting
+}
+
 }  // namespace
 
 extern "C" int osgpu_last_path(void) { return t_last_path; }
@@ -1045,6 +1259,24 @@ extern "C" void osgpu_reduce_scatter(int type, int op, void *target, const void 
 }
 
 extern "C" int osgpu_has_reduce_scatter(int type, int op)
+{
+    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+}
+
+// ======================================================================
+// Part 1e: batched reduce-to-all (no reference counterpart)
+// ======================================================================
+
+extern "C" void osgpu_reduce_many(int type, int op, int count, void *const *targets,
+                                  const void *const *sources, const int *nreduces, int PE_start,
+                                  int logPE_stride, int PE_size, void *pWrk, long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    reduce_many("osgpu_reduce_many", type, op, count, targets, sources, nreduces, PE_start,
+                logPE_stride, PE_size, pSync);
+}
+
+extern "C" int osgpu_has_reduce_many(int type, int op)
 {
     return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
 }

@@ -157,6 +157,10 @@ def load() -> ctypes.CDLL:
     L.osgpu_reduce_scatter.argtypes = [i, i, vp, vp, i, i, i, i, vp, vp]
     L.osgpu_reduce_scatter.restype = None
     L.osgpu_has_reduce_scatter.argtypes = [i, i]
+    L.osgpu_combine_many.argtypes = [i, i, i, vp, vp, i, vp, vp]
+    L.osgpu_reduce_many.argtypes = [i, i, i, vp, vp, vp, i, i, i, vp, vp]
+    L.osgpu_reduce_many.restype = None
+    L.osgpu_has_reduce_many.argtypes = [i, i]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -379,6 +383,37 @@ def reduce_scatter(t: str, op: str):
     receives of a source of PE_size * nreduce."""
     f, tc, oc = load().osgpu_reduce_scatter, type_code(t), OPS.index(op)
     return lambda *args: f(tc, oc, *args)
+
+
+def combine_many(t: str, op: str, targets, srcs, nelems, stream: int | None = None,
+                 check: bool = True) -> int:
+    """Enqueue osgpu_combine_many: targets[i] = fold(op, srcs[i]...) over
+    nelems[i] elements (device ptrs; every srcs[i] holds the same number of
+    inputs).  Returns the status; check=True raises on a non-zero one."""
+    L = load()
+    n = len(targets)
+    nsrc = len(srcs[0]) if n else 1
+    assert all(len(r) == nsrc for r in srcs), "one nsrc per call"
+    rows = [(ctypes.c_void_p * nsrc)(*r) for r in srcs]
+    tab = (ctypes.c_void_p * n)(*[ctypes.addressof(r) for r in rows])
+    rc = L.osgpu_combine_many(type_code(t), OPS.index(op), n, (ctypes.c_void_p * n)(*targets), tab,
+                              nsrc, (ctypes.c_size_t * n)(*nelems), stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_combine_many({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
+
+
+def reduce_many(t: str, op: str):
+    """osgpu_reduce_many bound to the codes of (t, op): a function
+    (targets, sources, nreduces, PE_start, logPE_stride, PE_size, pWrk, pSync)
+    over Python lists of addresses and counts."""
+    f, tc, oc = load().osgpu_reduce_many, type_code(t), OPS.index(op)
+
+    def call(targets, sources, nreduces, *rest):
+        n = len(targets)
+        return f(tc, oc, n, (ctypes.c_void_p * n)(*targets), (ctypes.c_void_p * n)(*sources),
+                 (ctypes.c_int * n)(*nreduces), *rest)
+    return call
 
 
 def copy(dsts, srcs, nbytes, stream: int | None = None):
