@@ -86,6 +86,17 @@ hipError_t launch_team_longdouble(int op, int P, void *const *dsts, const void *
 // hipErrorNotSupported for long double (contiguous shards only).
 hipError_t launch_team_tiles(int type, int op, int P, void *const *dsts, const void *const *srcs,
                              size_t n, int m, int k, hipStream_t s, bool remote = false);
+// Owner-computes prefix scan over an active set of P PEs (2 <= P <= 8,
+// team.hip): for i < n, dsts[q][i] = srcs[0][i] op ... op srcs[q][i]
+// (exclusive = 0) or ... op srcs[q-1][i] (exclusive = 1; dsts[0][i] = the
+// op's identity), ascending for every q, one running fold per element.
+// srcs/dsts as launch_team's; they must not overlap.  Multi-launch above
+// max_launch_threads().  hipErrorNotSupported for long double.
+hipError_t launch_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
+                            const void *const *srcs, size_t n, hipStream_t s);
+// n elements of the identity of (type, op) (scan_host.hpp scan_identity) at
+// dst, any alignment; long double's padding bytes zero (team.hip)
+hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s);
 
 // Byte copy of up to kMaxCopySegs independent ranges in one launch (copy.hip):
 // the data movement of broadcast / collect / fcollect / alltoall.  Sources may

@@ -1605,6 +1605,28 @@ int osgpu_team_combine_shape(int type, int op, int P, void *const *dsts, const v
     return OSGPU_OK;
 }
 
+int osgpu_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
+                    const void *const *srcs, size_t nelems, void *hip_stream)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)) || exclusive < 0 || exclusive > 1 || P < 2 ||
+        P > osgpu::kMaxTeam || !dsts || !srcs) {
+        set_err("osgpu_team_scan: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    if (type == OSGPU_T_LONGDOUBLE) {
+        set_err("osgpu_team_scan: no team scan kernel for long double (osgpu_scan takes the "
+                "pull form)");
+        return OSGPU_ENOTSUP;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_team_scan");
+    hipError_t e = osgpu::launch_team_scan(type, op, exclusive, P, dsts, srcs, nelems, st);
+    if (e != hipSuccess) {
+        set_err("osgpu_team_scan: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
 int osgpu_copy(void *const *dsts, const void *const *srcs, const size_t *bytes, int n,
                void *hip_stream)
 {

@@ -43,6 +43,7 @@
 #include "many_host.hpp"
 #include "rscatter_host.hpp"
 #include "runtime.hpp"
+#include "scan_host.hpp"
 
 namespace {
 
@@ -1149,6 +1150,240 @@ void reduce_many(const char *name, int type, int op, int count, void *const *tar
     run_many_pull(c, m);  // under every OSGPU_REDUCE_PATH setting
 }
 
+// ---------------------------------------------------------- prefix scans
+//
+// osgpu_scan: member m of the set receives the fold of the sources of members
+// 0..m (inclusive) or 0..m-1 (exclusive; member 0 the op's identity), in
+// ascending member order for EVERY member -- bit for bit what member 0 would
+// receive from the reduce-to-all over the sub-set of those members.
+// Paths: device heaps the owner-computes team kernel (launch_team_scan) or the
+// pull form; host heaps the host fold and GETMEM.  No FUSED, STAGED, RCCL or
+// push form, no long double team form, no local merge.
+// The byte arithmetic and the identities are scan_host.hpp's.
+
+static_assert((int) SCAN_T_SHORT == (int) OSGPU_T_SHORT &&
+                  (int) SCAN_T_LONGDOUBLE == (int) OSGPU_T_LONGDOUBLE &&
+                  (int) SCAN_T_COMPLEXD == (int) OSGPU_T_COMPLEXD &&
+                  (int) SCAN_T_HALF == (int) OSGPU_T_HALF &&
+                  (int) SCAN_T_BFLOAT16 == (int) OSGPU_T_BFLOAT16 &&
+                  (int) SCAN_OP_SUM == (int) OSGPU_OP_SUM && (int) SCAN_OP_XOR == (int) OSGPU_OP_XOR &&
+                  (int) SCAN_OP_MIN == (int) OSGPU_OP_MIN,
+              "scan_host.hpp repeats the codes of osgpu_reduce.h");
+
+// long double: bytes 10..15 of every slot a COPY wrote are zero, as after a fold
+void zero_ld_padding(const Call &c, void *p)
+{
+    if (c.type != osgpu::T_LONGDOUBLE) return;
+    for (size_t i = 0; i < (size_t) c.nreduce; i++) memset((char *) p + 16 * i + 10, 0, 6);
+}
+
+// TEAM: every member launches the scan kernel over its own contiguous shard
+// of all P targets, between the two barriers.  (No tiles / merge scheme of
+// local members: run_team's bookkeeping is the reduce-to-all's.)
+void run_scan_team(const Call &c, int excl, const std::vector<const void *> &srcs,
+                   const std::vector<void *> &dsts, int idx)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const size_t s = type_size(c.type);
+    const int P = c.PE_size;
+    t_last_path = OSGPU_RAN_TEAM;
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready, every target writable
+    long long lo = 0, hi = 0;
+    shard_of(c.nreduce, P, idx, s, &lo, &hi);
+    std::vector<const void *> sp(P);
+    std::vector<void *> dp(P);
+    for (int i = 0; i < P; i++) {
+        sp[i] = (const char *) srcs[i] + (size_t) lo * s;
+        dp[i] = (char *) dsts[i] + (size_t) lo * s;
+    }
+    DBG("%s PE %d: team scan, [%lld, %lld) of %d, P=%d, exclusive %d", c.name, c.me, lo, hi,
+        c.nreduce, P, excl);
+    if (hi > lo)
+        launched(c.name, "team scan launch",
+                 osgpu::launch_team_scan(c.type, c.op, excl, P, dp.data(), sp.data(),
+                                         (size_t) (hi - lo), st));
+    stream_wait(c.name, st);
+    barrier(c);  // every shard of my target is written
+}
+
+// PULL: member m folds the sources of the first K = scan_prefix_len members
+// itself, ascending (launch_combine_shifted: the target may sit at another
+// 16-byte phase); one input is a copy, none the identity fill.
+void run_scan_pull(const Call &c, int excl)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int K = scan_prefix_len(c.index_of(c.me), excl);
+    int seg = -1;
+    size_t off = 0;
+    bool ok = heap_locate(c.me, c.source, c.nbytes, &seg, &off);
+    std::vector<const void *> srcs(K);
+    for (int k = 0, pe = c.PE_start; ok && k < K; k++, pe += c.step) {
+        char *p = nullptr;
+        ok = heap_peer(pe, seg, off, c.nbytes, &p);
+        srcs[k] = p;
+    }
+    if (!ok)
+        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
+                      "(osgpu_heap_create / osgpu_heap_register) and the %zu-byte source inside it",
+              c.nbytes);
+    t_last_path = OSGPU_RAN_PULL;
+    DBG("%s PE %d: pull scan over %d members, exclusive %d", c.name, c.me, K, excl);
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready
+    // (member 0's identity too: peers read the source its target may overlap)
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const DeviceOut out(c, c.target, overlap, c.nbytes);
+    if (K == 0)
+        launched(c.name, "identity fill launch",
+                 osgpu::launch_scan_fill(c.type, c.op, out.out, (size_t) c.nreduce, st));
+    else
+        launched(c.name, "combine launch",
+                 osgpu::launch_combine_shifted(c.type, c.op, out.out, srcs.data(), K,
+                                               (size_t) c.nreduce, st));
+    stream_wait(c.name, st);
+    barrier(c);  // peers are done reading my source
+    out.finish(c.nbytes, st);
+}
+
+// member j's source as member m sees it on a host heap: its own array, or
+// one getmem of `nb` bytes from `off` into `buf`
+const void *scan_host_input(const Call &c, int j, size_t off, size_t nb, void *buf)
+{
+    const int pe = c.PE_start + j * c.step;
+    const char *src = (const char *) c.source + off;
+    if (pe == c.me) return src;
+    c.ops.getmem(buf, src, nb, pe);
+    return buf;
+}
+
+// Host heaps, the last member's pull ((P - 1) arrays) at most
+// host_fold_max_bytes(): the fold on this PE's thread, one getmem of the
+// whole array per peer it folds.
+void run_scan_host_fold(const Call &c, int excl)
+{
+    t_last_path = OSGPU_RAN_HOST_FOLD;
+    const int K = scan_prefix_len(c.index_of(c.me), excl);
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    thread_local std::vector<unsigned char> tmp, peer;
+    if (overlap) tmp.resize(c.nbytes);
+    if (K > 0) peer.resize(c.nbytes);
+    void *acc = overlap ? (void *) tmp.data() : c.target;
+    barrier(c);  // every source is ready
+    if (K == 0) {
+        if (!scan_fill_identity(c.type, c.op, acc, (size_t) c.nreduce))
+            fatal(c.name, "no identity for type %d op %d", c.type, c.op);
+    } else {
+        memmove(acc, scan_host_input(c, 0, 0, c.nbytes, peer.data()), c.nbytes);
+        if (K == 1) zero_ld_padding(c, acc);
+        for (int j = 1; j < K; j++)
+            if (!osgpu::host_fold(c.type, c.op, acc, scan_host_input(c, j, 0, c.nbytes, peer.data()),
+                                  (size_t) c.nreduce))
+                fatal(c.name, "host fold: type %d op %d", c.type, c.op);
+    }
+    barrier(c);  // every peer is done reading my source
+    if (overlap) memcpy(c.target, acc, c.nbytes);
+}
+
+// Host heaps above that: the K inputs pulled in chunks of host_chunk_bytes()
+// into pinned staging, combined on the GPU.  Member 0 of an exclusive scan
+// writes the identity on the host.
+void run_scan_host(const Call &c, int excl)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
+    const int K = scan_prefix_len(c.index_of(c.me), excl);
+    t_last_path = OSGPU_RAN_GETMEM;
+    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    HostTmp result(c, c.target, overlap, c.nbytes);
+    barrier(c);  // every source is ready
+    if (K == 0) {
+        if (!scan_fill_identity(c.type, c.op, result.out, N))
+            fatal(c.name, "no identity for type %d op %d", c.type, c.op);
+    } else {
+        const size_t chunk = scan_chunk_elems(host_chunk_bytes(), s, N), cb = chunk * s;
+        char *dbuf = (char *) device_scratch(c.name, c.me, cb * (K + 1));
+        char *hbuf = (char *) host_stage(c.name, c.me, cb * (K + 1));
+        std::vector<const void *> srcs(K);
+        for (int k = 0; k < K; k++) srcs[k] = dbuf + (size_t) k * cb;
+        scan_for_chunks(N, chunk, [&](size_t off, size_t n) {
+            const size_t nb = n * s;
+            for (int k = 0; k < K; k++) {
+                char *hk = hbuf + (size_t) k * cb;
+                const void *in = scan_host_input(c, k, off * s, nb, hk);
+                if (in != hk) memcpy(hk, in, nb);
+                HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
+            }
+            // (a slot of cb bytes need not be a multiple of 16: the slots' phases may differ)
+            char *dout = dbuf + (size_t) K * cb, *hout = hbuf + (size_t) K * cb;
+            launched(c.name, "combine launch",
+                     osgpu::launch_combine_shifted(c.type, c.op, dout, srcs.data(), K, n, st));
+            HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
+            stream_wait(c.name, st);
+            memcpy(result.out + off * s, hout, nb);
+        });
+    }
+    barrier(c);  // every peer is done reading my source
+    result.finish(c.nbytes);
+}
+
+void scan(const char *name, int type, int op, int exclusive, void *target, const void *source,
+          int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)))
+        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_scan)", type, op);
+    if (exclusive != 0 && exclusive != 1)
+        fatal(name, "exclusive is %d: 0 (inclusive) or 1 (exclusive)", exclusive);
+    Call c;
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    c.target = target;
+    c.source = const_cast<void *>(source);
+    c.nreduce = nreduce;
+    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
+        t_last_path = OSGPU_RAN_BARRIER_ONLY;
+        sync_only(c);
+        return;
+    }
+    ScanBytes b;
+    if (!scan_bytes(type_size(type), nreduce, PE_size, c.index_of(c.me), exclusive, &b))
+        fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
+    c.nbytes = b.bytes;
+
+    int dt = -1, ds = -1;
+    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
+    if (kt != ks)
+        fatal(name, "target and source must both be device or both be host memory");
+    if (kt == MEM_HOST) {
+        const int hp = host_path();
+        require_host_heaps(c);
+        // a size every member shares: all of them take the same path
+        const size_t fold_lim = host_fold_max_bytes();  // 0: off
+        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
+            osgpu::host_fold_supported(type, op)) {
+            run_scan_host_fold(c, exclusive);
+            return;
+        }
+        if (hp == OSGPU_HOST_STAGED)
+            DBG("%s PE %d: no STAGED form of the scan, taking GETMEM", name, c.me);
+        run_scan_host(c, exclusive);
+        return;
+    }
+    const DeviceGuard on_device(name, dt);
+    std::vector<const void *> srcs;
+    std::vector<void *> dsts;
+    int idx = -1;
+    // the team kernel under every setting but OSGPU_PATH_PULL (RCCL never
+    // serves a scan); long double, an overlap, a target outside the heaps
+    // and more than 8 members take the pull form
+    if (path_mode() != OSGPU_PATH_PULL && type != OSGPU_T_LONGDOUBLE &&
+        (idx = team_ptrs(c, srcs, dsts)) >= 0)
+        run_scan_team(c, exclusive, srcs, dsts, idx);
+    else
+        run_scan_pull(c, exclusive);
+}
+
 }  // namespace
 
 extern "C" int osgpu_last_path(void) { return t_last_path; }
@@ -1279,4 +1514,35 @@ extern "C" void osgpu_reduce_many(int type, int op, int count, void *const *targ
 extern "C" int osgpu_has_reduce_many(int type, int op)
 {
     return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+}
+
+// ======================================================================
+// Part 1f: prefix scans across PEs (no reference counterpart)
+// ======================================================================
+
+extern "C" void osgpu_scan(int type, int op, int exclusive, void *target, const void *source,
+                           int nreduce, int PE_start, int logPE_stride, int PE_size, void *pWrk,
+                           long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    scan("osgpu_scan", type, op, exclusive, target, source, nreduce, PE_start, logPE_stride,
+         PE_size, pSync);
+}
+
+extern "C" int osgpu_has_scan(int type, int op)
+{
+    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+}
+
+extern "C" int osgpu_scan_identity(int type, int op, void *elem_out)
+{
+    unsigned char id[16];
+    const size_t s = osgpu::rt::scan_identity(type, op, id);
+    if (!elem_out || !s || !osgpu_has_scan(type, op)) {
+        osgpu::rt::set_err("osgpu_scan_identity: type %d op %d is not a reduction of this library",
+                           type, op);
+        return OSGPU_EINVAL;
+    }
+    memcpy(elem_out, id, s);
+    return OSGPU_OK;
 }

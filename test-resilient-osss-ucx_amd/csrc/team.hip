@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "kernel_common.hpp"
+#include "scan_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -550,6 +551,261 @@ hipError_t launch_team(int type, int op, int P, void *const *dsts, const void *c
                        size_t n, hipStream_t s, bool remote)
 {
     return launch_team_tiles(type, op, P, dsts, srcs, n, 1, 0, s, remote);
+}
+
+// ------------------------------------------------------------ prefix scan
+// osgpu_scan: member q of the set receives the fold of members 0..q
+// (inclusive) or 0..q-1 (exclusive), ascending for every member.  The same
+// owner-computes shape as above -- this member reads its shard of every
+// source once and writes that shard of every target -- but one running fold
+// serves every output: P - 1 operations per element, where the ordered team
+// fold takes P (P - 1).  `excl` (0 / 1) is a kernel argument: wave-uniform,
+// one instantiation serves both modes.  `ident`: the op's identity in every
+// element of a vector (scan_host.hpp), stored to member 0 by an exclusive
+// scan and never an operand.
+
+// The scan of one element: x[q] of the first np members in, store(q, value)
+// out, by the exact element ops.  N is the array's size; np <= N.
+template <typename T, int OP, int N, typename St>
+__device__ __forceinline__ void scan_elem(const T (&x)[N], int np, int excl, T ident, St &&store)
+{
+    T acc = x[0];
+    store(0, excl ? ident : acc);
+#pragma unroll
+    for (int q = 1; q < N; q++) {
+        if (q >= np) break;
+        const T inc = Elem<T, OP>::f(acc, x[q]);
+        store(q, excl ? acc : inc);
+        acc = inc;
+    }
+}
+
+// LDS-staged form, the shape of team_lds_kernel: P waves per workgroup, a
+// tile of 64*U 16-B vectors per member.  Wave p streams member p's source
+// tile into LDS; after the barrier wave q folds inputs 0 .. q - excl from LDS
+// ascending and streams member q's target tile.  No input: the identity
+// vector; one: a copy.  HBM bytes as the team kernel (2*P*s per element).
+template <typename T, int OP, int P, int U>
+__global__ __launch_bounds__(64 * P) void team_scan_lds_kernel(TeamPtrs<T, P> a, size_t nvec,
+                                                               size_t head, size_t tail_start,
+                                                               int nedge, int excl, u32x4 ident)
+{
+    constexpr int W = 16 / sizeof(T);
+    constexpr int V = 64 * U;  // vectors per member per tile
+    __shared__ u32x4 tile[P][V];
+    if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
+        const size_t e = edge_index(head, tail_start);
+        T x[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) x[p] = a.src[p][e];
+        Vec16<T> id;
+        id.v = ident;
+        scan_elem<T, OP>(x, P, excl, id.e[0], [&](int q, T r) { a.dst[q][e] = r; });
+    }
+    // the member this wave stages and writes
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63);
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(pick(a.src, w) + head);
+    u32x4 *dst = reinterpret_cast<u32x4 *>(pick(a.dst, w) + head);
+    const size_t base = (size_t) blockIdx.x * V;
+    const bool whole = base + V <= nvec;
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        v[u] = u32x4{0, 0, 0, 0};
+        if (whole || base + u * 64 + lane < nvec)
+            v[u] = __builtin_nontemporal_load(src + base + u * 64 + lane);
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) tile[w][u * 64 + lane] = v[u];
+    __syncthreads();
+    using F = Fast<T, OP>;
+    const int nin = w + 1 - excl;  // inputs of this wave's output: 0 .. P
+    Rounds<0, P + 1>::run([&](auto nc) {
+        constexpr int N = decltype(nc)::value;
+        if (nin != N) return;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (!whole && base + u * 64 + lane >= nvec) continue;
+            Vec16<T> out;
+            if constexpr (N == 0) {
+                out.v = ident;
+            } else if constexpr (N == 1) {
+                out.v = tile[0][u * 64 + lane];
+            } else {
+                Vec16<T> in[N];
+#pragma unroll
+                for (int p = 0; p < N; p++) in[p].v = tile[p][u * 64 + lane];
+                // the branch-free fold first, the exact one only for a vector
+                // whose result holds a NaN part (elem_ops.hpp Fast)
+                bool bad = false;
+#pragma unroll
+                for (int e = 0; e < W; e++) {
+                    T acc = in[0].e[e];
+#pragma unroll
+                    for (int k = 1; k < N; k++) acc = F::f(acc, in[k].e[e]);
+                    out.e[e] = acc;
+                    bad = bad || F::bad(acc);
+                }
+                if (F::kChecked && __builtin_expect(bad, 0)) {
+#pragma unroll
+                    for (int e = 0; e < W; e++) {
+                        T acc = in[0].e[e];
+#pragma unroll
+                        for (int k = 1; k < N; k++) acc = Elem<T, OP>::f(acc, in[k].e[e]);
+                        out.e[e] = acc;
+                    }
+                }
+            }
+            __builtin_nontemporal_store(out.v, dst + base + u * 64 + lane);
+        }
+    });
+}
+
+// element-granular form (pointers whose 16-byte phases differ): np members
+// of a table sized for kMaxTeam, so one instantiation serves every P
+template <typename T, int OP>
+__global__ __launch_bounds__(kTeamBlock) void team_scan_scalar_kernel(TeamPtrs<T, kMaxTeam> a,
+                                                                      int np, size_t n, int excl,
+                                                                      u32x4 ident)
+{
+    Vec16<T> id;
+    id.v = ident;
+    const size_t stride = (size_t) gridDim.x * kTeamBlock;
+    for (size_t i = (size_t) blockIdx.x * kTeamBlock + threadIdx.x; i < n; i += stride) {
+        T x[kMaxTeam];
+#pragma unroll
+        for (int p = 0; p < kMaxTeam; p++)
+            if (p < np) x[p] = a.src[p][i];
+        scan_elem<T, OP>(x, np, excl, id.e[0], [&](int q, T r) { a.dst[q][i] = r; });
+    }
+}
+
+// byte k % s (s = 2, 4, 8 or 16) of a 16-byte pattern, without indexing registers
+__device__ __forceinline__ unsigned pattern_byte(u32x4 pat, size_t k, unsigned s)
+{
+    const unsigned i = (unsigned) (k % s), wd = i >> 2;
+    const unsigned word = wd == 0 ? pat.x : (wd == 1 ? pat.y : (wd == 2 ? pat.z : pat.w));
+    return (word >> (8 * (i & 3))) & 0xffu;
+}
+
+// The identity fill: nbytes from dst, byte k = elem's byte k % s.  Bytes
+// [0, head) up to the first 16-byte boundary and the bytes behind the last
+// whole vector go one per lane of workgroup 0 (fewer than 32); the nvec
+// vectors between are 16-byte stores of `vec`, the pattern as it falls on a
+// 16-byte boundary.
+__global__ __launch_bounds__(kTeamBlock) void scan_fill_kernel(unsigned char *dst, size_t nbytes,
+                                                               size_t head, size_t nvec, u32x4 vec,
+                                                               u32x4 elem, unsigned s)
+{
+    const size_t tail_start = head + nvec * 16;
+    const size_t nedge = head + (nbytes - tail_start);
+    if (blockIdx.x == 0 && threadIdx.x < nedge) {
+        const size_t k = edge_index(head, tail_start);
+        dst[k] = (unsigned char) pattern_byte(elem, k, s);
+    }
+    const size_t stride = (size_t) gridDim.x * kTeamBlock;
+    u32x4 *out = reinterpret_cast<u32x4 *>(dst + head);
+    for (size_t j = (size_t) blockIdx.x * kTeamBlock + threadIdx.x; j < nvec; j += stride)
+        __builtin_nontemporal_store(vec, out + j);
+}
+
+// 16 bytes of the pattern of period s starting at its byte `at`
+static u32x4 pattern_vec(const unsigned char *elem, size_t s, size_t at)
+{
+    unsigned char b[16];
+    for (size_t i = 0; i < 16; i++) b[i] = elem[(at + i) % s];
+    u32x4 v;
+    memcpy(&v, b, 16);
+    return v;
+}
+
+hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s)
+{
+    unsigned char id[16];
+    const size_t es = rt::scan_identity(type, op, id);
+    if (!es) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const size_t nbytes = n * es, phase = (uintptr_t) dst & 15;
+    size_t head = phase ? 16 - phase : 0;
+    if (head > nbytes) head = nbytes;
+    const size_t nvec = (nbytes - head) / 16;
+    size_t blocks = (nvec + kTeamBlock - 1) / kTeamBlock;
+    blocks = blocks > 8192 ? 8192 : (blocks ? blocks : 1);
+    hipLaunchKernelGGL(scan_fill_kernel, dim3((unsigned) blocks), dim3(kTeamBlock), 0, s,
+                       static_cast<unsigned char *>(dst), nbytes, head, nvec,
+                       pattern_vec(id, es, head), pattern_vec(id, es, 0), (unsigned) es);
+    return hipGetLastError();
+}
+
+template <typename T, int OP, int P>
+static hipError_t scan_launch_p(void *const *dsts, const void *const *srcs, const VecSplit &vs,
+                                int excl, u32x4 ident, hipStream_t s)
+{
+    constexpr int W = 16 / sizeof(T);
+    constexpr int UL = OSGPU_TEAM_LDS_U;
+    constexpr size_t V = (size_t) 64 * UL;
+    // one tile per workgroup of P waves, in runs below the launch limit
+    // (for_each_tile_run): the first launch takes the edges, the others
+    // shifted pointers
+    return for_each_tile_run(vs.nvec, V, 64 * P, 1, [&](size_t t0, size_t nt, size_t nv) {
+        const size_t off = t0 == 0 ? 0 : vs.head + t0 * V * W;
+        TeamPtrs<T, P> a;
+        for (int p = 0; p < P; p++) {
+            a.src[p] = static_cast<const T *>(srcs[p]) + off;
+            a.dst[p] = static_cast<T *>(dsts[p]) + off;
+        }
+        hipLaunchKernelGGL((team_scan_lds_kernel<T, OP, P, UL>), dim3((unsigned) nt),
+                           dim3(64 * P), 0, s, a, nv, t0 == 0 ? vs.head : (size_t) 0,
+                           t0 == 0 ? vs.tail_start : (size_t) 0, t0 == 0 ? vs.nedge : 0, excl,
+                           ident);
+        return hipGetLastError();
+    });
+}
+
+template <typename T, int OP>
+static hipError_t scan_launch_op(int P, void *const *d, const void *const *sr, size_t n, int excl,
+                                 u32x4 ident, hipStream_t s)
+{
+    const VecSplit vs = vec_split(sizeof(T), n, sr, P, d, P);
+    if (!vs.vec) {
+        TeamPtrs<T, kMaxTeam> a;
+        for (int p = 0; p < kMaxTeam; p++) {
+            a.src[p] = p < P ? static_cast<const T *>(sr[p]) : nullptr;
+            a.dst[p] = p < P ? static_cast<T *>(d[p]) : nullptr;
+        }
+        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
+        blocks = blocks > 8192 ? 8192 : blocks;
+        hipLaunchKernelGGL((team_scan_scalar_kernel<T, OP>), dim3((unsigned) blocks),
+                           dim3(kTeamBlock), 0, s, a, P, n, excl, ident);
+        return hipGetLastError();
+    }
+    switch (P) {
+    case 2: return scan_launch_p<T, OP, 2>(d, sr, vs, excl, ident, s);
+    case 3: return scan_launch_p<T, OP, 3>(d, sr, vs, excl, ident, s);
+    case 4: return scan_launch_p<T, OP, 4>(d, sr, vs, excl, ident, s);
+    case 5: return scan_launch_p<T, OP, 5>(d, sr, vs, excl, ident, s);
+    case 6: return scan_launch_p<T, OP, 6>(d, sr, vs, excl, ident, s);
+    case 7: return scan_launch_p<T, OP, 7>(d, sr, vs, excl, ident, s);
+    case 8: return scan_launch_p<T, OP, 8>(d, sr, vs, excl, ident, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
+                            const void *const *srcs, size_t n, hipStream_t s)
+{
+    if (P < 2 || P > kMaxTeam || exclusive < 0 || exclusive > 1) return hipErrorInvalidValue;
+    if (type == T_LONGDOUBLE) return hipErrorNotSupported;
+    unsigned char id[16];
+    const size_t es = rt::scan_identity(type, op, id);
+    if (!es) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const u32x4 ident = pattern_vec(id, es, 0);
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        return scan_launch_op<typename decltype(t)::type, decltype(o)::value>(P, dsts, srcs, n,
+                                                                              exclusive, ident, s);
+    });
 }
 
 }  // namespace osgpu

@@ -161,6 +161,11 @@ def load() -> ctypes.CDLL:
     L.osgpu_reduce_many.argtypes = [i, i, i, vp, vp, vp, i, i, i, vp, vp]
     L.osgpu_reduce_many.restype = None
     L.osgpu_has_reduce_many.argtypes = [i, i]
+    L.osgpu_scan.argtypes = [i, i, i, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_scan.restype = None
+    L.osgpu_has_scan.argtypes = [i, i]
+    L.osgpu_scan_identity.argtypes = [i, i, vp]
+    L.osgpu_team_scan.argtypes = [i, i, i, i, vp, vp, sz, vp]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -414,6 +419,40 @@ def reduce_many(t: str, op: str):
         return f(tc, oc, n, (ctypes.c_void_p * n)(*targets), (ctypes.c_void_p * n)(*sources),
                  (ctypes.c_int * n)(*nreduces), *rest)
     return call
+
+
+def scan(t: str, op: str, exclusive: bool):
+    """osgpu_scan bound to the codes of (t, op) and the mode: a function with
+    the arguments of shmem_<t>_<op>_to_all (target, source, nreduce, PE_start,
+    logPE_stride, PE_size, pWrk, pSync); member m receives the fold of members
+    0..m (inclusive) or 0..m-1 (exclusive) in ascending order."""
+    f, tc, oc, ex = load().osgpu_scan, type_code(t), OPS.index(op), int(bool(exclusive))
+    return lambda *args: f(tc, oc, ex, *args)
+
+
+def scan_identity(t: str, op: str) -> bytes:
+    """osgpu_scan_identity: the identity of (t, op) as one element's bytes;
+    raises for a pair that is no reduction."""
+    L = load()
+    buf = ctypes.create_string_buffer(16)
+    rc = L.osgpu_scan_identity(type_code(t), OPS.index(op), buf)
+    if rc != 0:
+        raise ValueError(L.osgpu_last_error().decode())
+    return buf.raw[:L.osgpu_type_size(type_code(t))]
+
+
+def team_scan(t: str, op: str, exclusive: bool, dsts, srcs, n: int, stream: int | None = None,
+              check: bool = True) -> int:
+    """Enqueue the owner-computes scan kernel: dsts[q] = srcs[0] op ... op
+    srcs[q] (exclusive: ... srcs[q-1], dsts[0] the identity) (device ptrs).
+    Returns the status; check=True raises on a non-zero one."""
+    L = load()
+    P = len(srcs)
+    rc = L.osgpu_team_scan(type_code(t), OPS.index(op), int(bool(exclusive)), P,
+                           (ctypes.c_void_p * P)(*dsts), (ctypes.c_void_p * P)(*srcs), n, stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_team_scan({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
 
 
 def copy(dsts, srcs, nbytes, stream: int | None = None):
