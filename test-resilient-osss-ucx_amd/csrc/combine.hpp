@@ -94,6 +94,16 @@ hipError_t launch_team_tiles(int type, int op, int P, void *const *dsts, const v
 // max_launch_threads().  hipErrorNotSupported for long double.
 hipError_t launch_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
                             const void *const *srcs, size_t n, hipStream_t s);
+// Owner-computes uniform reduce-to-all over an active set of P PEs
+// (2 <= P <= 8, team.hip): for i < n and every q < P,
+// dsts[q][i] = srcs[0][i] op ... op srcs[P-1][i], ONE ascending fold per
+// element stored to all P targets.  srcs/dsts as launch_team's; they must not
+// overlap.  Multi-launch above max_launch_threads().  Long double:
+// launch_uniform_longdouble (longdouble.hip; pointers 8-byte aligned).
+hipError_t launch_team_uniform(int type, int op, int P, void *const *dsts,
+                               const void *const *srcs, size_t n, hipStream_t s);
+hipError_t launch_uniform_longdouble(int op, int P, void *const *dsts, const void *const *srcs,
+                                     size_t n, hipStream_t s);
 // n elements of the identity of (type, op) (scan_host.hpp scan_identity) at
 // dst, any alignment; long double's padding bytes zero (team.hip)
 hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s);

@@ -272,4 +272,74 @@ hipError_t launch_team_longdouble(int op, int P, void *const *dsts, const void *
     });
 }
 
+namespace x87 {
+
+// uniform form (team.hip launch_team_uniform): ONE ascending fold of the P
+// inputs, P - 1 soft ops per element where ld_team_kernel takes P (P - 1),
+// by the ops of ld_vec_kernel; the packed result goes to all P targets.
+// VEC: 16-byte aligned arrays, one dwordx4 per element and array.
+template <int OP, int P, bool VEC>
+__global__ __launch_bounds__(256) void ld_uniform_kernel(LdTeam a, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        X80 x[P];
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            x[p] = VEC ? unpack(__builtin_nontemporal_load(
+                             reinterpret_cast<const u64x2 *>(a.src[p]) + i))
+                       : load(a.src[p] + 16 * i);
+        X80 acc = x[0];
+#pragma unroll
+        for (int p = 1; p < P; p++) acc = apply<OP>(acc, x[p]);
+#pragma unroll
+        for (int q = 0; q < P; q++) {
+            if (VEC)
+                __builtin_nontemporal_store(pack(acc), reinterpret_cast<u64x2 *>(a.dst[q]) + i);
+            else
+                store(a.dst[q] + 16 * i, acc);
+        }
+    }
+}
+
+template <int OP>
+hipError_t ld_uniform_launch(int P, bool vec, const LdTeam &a, size_t n, unsigned blocks,
+                             hipStream_t s)
+{
+    switch (P) {
+#define LDU(PP)                                                                \
+    case PP:                                                                   \
+        if (vec)                                                               \
+            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, true>), dim3(blocks), dim3(256), 0, s, a, n); \
+        else                                                                   \
+            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, false>), dim3(blocks), dim3(256), 0, s, a, n); \
+        return hipGetLastError();
+        LDU(2) LDU(3) LDU(4) LDU(5) LDU(6) LDU(7) LDU(8)
+#undef LDU
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace x87
+
+hipError_t launch_uniform_longdouble(int op, int P, void *const *dsts, const void *const *srcs,
+                                     size_t n, hipStream_t s)
+{
+    if (P < 2 || P > kMaxTeam) return hipErrorInvalidValue;
+    x87::LdTeam a;
+    bool vec = true;
+    for (int p = 0; p < P; p++) {
+        a.src[p] = (const unsigned char *) srcs[p];
+        a.dst[p] = (unsigned char *) dsts[p];
+        if ((((uintptr_t) srcs[p]) | ((uintptr_t) dsts[p])) & 7) return hipErrorInvalidValue;
+        vec = vec && ((((uintptr_t) srcs[p]) | ((uintptr_t) dsts[p])) & 15) == 0;
+    }
+    if (n == 0) return dispatch_ld_op(op, hipErrorInvalidValue, [](auto) { return hipSuccess; });
+    size_t blocks = (n + 255) / 256;
+    blocks = blocks > 16384 ? 16384 : blocks;
+    return dispatch_ld_op(op, hipErrorInvalidValue, [&](auto o) {
+        return x87::ld_uniform_launch<decltype(o)::value>(P, vec, a, n, (unsigned) blocks, s);
+    });
+}
+
 }  // namespace osgpu

@@ -1627,6 +1627,23 @@ int osgpu_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
     return OSGPU_OK;
 }
 
+int osgpu_team_uniform(int type, int op, int P, void *const *dsts, const void *const *srcs,
+                       size_t nelems, void *hip_stream)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)) || P < 2 || P > osgpu::kMaxTeam || !dsts ||
+        !srcs) {
+        set_err("osgpu_team_uniform: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_team_uniform");
+    hipError_t e = osgpu::launch_team_uniform(type, op, P, dsts, srcs, nelems, st);
+    if (e != hipSuccess) {
+        set_err("osgpu_team_uniform: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
 int osgpu_copy(void *const *dsts, const void *const *srcs, const size_t *bytes, int n,
                void *hip_stream)
 {

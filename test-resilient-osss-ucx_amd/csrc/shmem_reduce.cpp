@@ -1207,13 +1207,13 @@ void run_scan_team(const Call &c, int excl, const std::vector<const void *> &src
     barrier(c);  // every shard of my target is written
 }
 
-// PULL: member m folds the sources of the first K = scan_prefix_len members
+// PULL of the first K members of the set: the caller folds their sources
 // itself, ascending (launch_combine_shifted: the target may sit at another
-// 16-byte phase); one input is a copy, none the identity fill.
-void run_scan_pull(const Call &c, int excl)
+// 16-byte phase); one input is a copy, none the identity fill.  The scan's
+// member m takes K = scan_prefix_len, the uniform reduce K = PE_size.
+void run_prefix_pull(const Call &c, int K)
 {
     hipStream_t st = pe_stream(c.name, c.me);
-    const int K = scan_prefix_len(c.index_of(c.me), excl);
     int seg = -1;
     size_t off = 0;
     bool ok = heap_locate(c.me, c.source, c.nbytes, &seg, &off);
@@ -1228,7 +1228,7 @@ void run_scan_pull(const Call &c, int excl)
                       "(osgpu_heap_create / osgpu_heap_register) and the %zu-byte source inside it",
               c.nbytes);
     t_last_path = OSGPU_RAN_PULL;
-    DBG("%s PE %d: pull scan over %d members, exclusive %d", c.name, c.me, K, excl);
+    DBG("%s PE %d: pull over the first %d members, ascending", c.name, c.me, K);
     entry_sync(c.name, st);
     barrier(c);  // every source is ready
     // (member 0's identity too: peers read the source its target may overlap)
@@ -1246,6 +1246,11 @@ void run_scan_pull(const Call &c, int excl)
     out.finish(c.nbytes, st);
 }
 
+void run_scan_pull(const Call &c, int excl)
+{
+    run_prefix_pull(c, scan_prefix_len(c.index_of(c.me), excl));
+}
+
 // member j's source as member m sees it on a host heap: its own array, or
 // one getmem of `nb` bytes from `off` into `buf`
 const void *scan_host_input(const Call &c, int j, size_t off, size_t nb, void *buf)
@@ -1258,12 +1263,12 @@ const void *scan_host_input(const Call &c, int j, size_t off, size_t nb, void *b
 }
 
 // Host heaps, the last member's pull ((P - 1) arrays) at most
-// host_fold_max_bytes(): the fold on this PE's thread, one getmem of the
-// whole array per peer it folds.
-void run_scan_host_fold(const Call &c, int excl)
+// host_fold_max_bytes(): the fold of the first K members on this PE's thread,
+// ascending -- the caller's own source in its place in the order -- one
+// getmem of the whole array per peer it folds.
+void run_prefix_host_fold(const Call &c, int K)
 {
     t_last_path = OSGPU_RAN_HOST_FOLD;
-    const int K = scan_prefix_len(c.index_of(c.me), excl);
     const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
     thread_local std::vector<unsigned char> tmp, peer;
     if (overlap) tmp.resize(c.nbytes);
@@ -1285,14 +1290,18 @@ void run_scan_host_fold(const Call &c, int excl)
     if (overlap) memcpy(c.target, acc, c.nbytes);
 }
 
+void run_scan_host_fold(const Call &c, int excl)
+{
+    run_prefix_host_fold(c, scan_prefix_len(c.index_of(c.me), excl));
+}
+
 // Host heaps above that: the K inputs pulled in chunks of host_chunk_bytes()
 // into pinned staging, combined on the GPU.  Member 0 of an exclusive scan
-// writes the identity on the host.
-void run_scan_host(const Call &c, int excl)
+// (K == 0) writes the identity on the host.
+void run_prefix_host(const Call &c, int K)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type), N = (size_t) c.nreduce;
-    const int K = scan_prefix_len(c.index_of(c.me), excl);
     t_last_path = OSGPU_RAN_GETMEM;
     const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
     HostTmp result(c, c.target, overlap, c.nbytes);
@@ -1325,6 +1334,11 @@ void run_scan_host(const Call &c, int excl)
     }
     barrier(c);  // every peer is done reading my source
     result.finish(c.nbytes);
+}
+
+void run_scan_host(const Call &c, int excl)
+{
+    run_prefix_host(c, scan_prefix_len(c.index_of(c.me), excl));
 }
 
 void scan(const char *name, int type, int op, int exclusive, void *target, const void *source,
@@ -1382,6 +1396,102 @@ void scan(const char *name, int type, int op, int exclusive, void *target, const
         run_scan_team(c, exclusive, srcs, dsts, idx);
     else
         run_scan_pull(c, exclusive);
+}
+
+// ------------------------------------------------- uniform reduce-to-all
+//
+// osgpu_reduce_uniform: every member receives the ONE ascending fold of all
+// members' sources -- member 0's reduce-to-all result, the last member's
+// inclusive scan -- so all targets hold the same bytes.  Paths: device heaps
+// the owner-computes uniform kernel (launch_team_uniform, long double
+// included) or the pull form; host heaps the host fold and GETMEM.  The pull
+// and host forms are the scan's over K = PE_size members: never
+// osgpu_fold_order's caller-first order.  No FUSED, STAGED, RCCL or push form.
+
+// TEAM: every member launches the uniform kernel over its own contiguous
+// shard of all P targets, between the two barriers.
+void run_uniform_team(const Call &c, const std::vector<const void *> &srcs,
+                      const std::vector<void *> &dsts, int idx)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const size_t s = type_size(c.type);
+    const int P = c.PE_size;
+    t_last_path = OSGPU_RAN_TEAM;
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready, every target writable
+    long long lo = 0, hi = 0;
+    shard_of(c.nreduce, P, idx, s, &lo, &hi);
+    std::vector<const void *> sp(P);
+    std::vector<void *> dp(P);
+    for (int i = 0; i < P; i++) {
+        sp[i] = (const char *) srcs[i] + (size_t) lo * s;
+        dp[i] = (char *) dsts[i] + (size_t) lo * s;
+    }
+    DBG("%s PE %d: team uniform, [%lld, %lld) of %d, P=%d", c.name, c.me, lo, hi, c.nreduce, P);
+    if (hi > lo)
+        launched(c.name, "team uniform launch",
+                 osgpu::launch_team_uniform(c.type, c.op, P, dp.data(), sp.data(),
+                                            (size_t) (hi - lo), st));
+    stream_wait(c.name, st);
+    barrier(c);  // every shard of my target is written
+}
+
+void run_uniform_pull(const Call &c) { run_prefix_pull(c, c.PE_size); }
+void run_uniform_host_fold(const Call &c) { run_prefix_host_fold(c, c.PE_size); }
+void run_uniform_host(const Call &c) { run_prefix_host(c, c.PE_size); }
+
+void reduce_uniform(const char *name, int type, int op, void *target, const void *source,
+                    int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    if (!(has_op(type, op) || has_ext_op(type, op)))
+        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_uniform)",
+              type, op);
+    Call c;
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    c.target = target;
+    c.source = const_cast<void *>(source);
+    c.nreduce = nreduce;
+    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
+        t_last_path = OSGPU_RAN_BARRIER_ONLY;
+        sync_only(c);
+        return;
+    }
+    ScanBytes b;  // the inclusive scan's byte counts: every member folds what its last one does
+    if (!scan_bytes(type_size(type), nreduce, PE_size, c.index_of(c.me), 0, &b))
+        fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
+    c.nbytes = b.bytes;
+
+    int dt = -1, ds = -1;
+    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
+    if (kt != ks)
+        fatal(name, "target and source must both be device or both be host memory");
+    if (kt == MEM_HOST) {
+        const int hp = host_path();
+        require_host_heaps(c);
+        const size_t fold_lim = host_fold_max_bytes();  // 0: off
+        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
+            osgpu::host_fold_supported(type, op)) {
+            run_uniform_host_fold(c);
+            return;
+        }
+        if (hp == OSGPU_HOST_STAGED)
+            DBG("%s PE %d: no STAGED form of the uniform reduce, taking GETMEM", name, c.me);
+        run_uniform_host(c);
+        return;
+    }
+    const DeviceGuard on_device(name, dt);
+    std::vector<const void *> srcs;
+    std::vector<void *> dsts;
+    int idx = -1;
+    // the team kernel under every setting but OSGPU_PATH_PULL (RCCL's order
+    // is not this one), for every type; an overlap, a target outside the
+    // heaps, one member and more than 8 take the pull form
+    if (path_mode() != OSGPU_PATH_PULL && (idx = team_ptrs(c, srcs, dsts)) >= 0)
+        run_uniform_team(c, srcs, dsts, idx);
+    else
+        run_uniform_pull(c);
 }
 
 }  // namespace
@@ -1545,4 +1655,22 @@ extern "C" int osgpu_scan_identity(int type, int op, void *elem_out)
     }
     memcpy(elem_out, id, s);
     return OSGPU_OK;
+}
+
+// ======================================================================
+// Part 1g: uniform reduce-to-all (no reference counterpart)
+// ======================================================================
+
+extern "C" void osgpu_reduce_uniform(int type, int op, void *target, const void *source,
+                                     int nreduce, int PE_start, int logPE_stride, int PE_size,
+                                     void *pWrk, long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    reduce_uniform("osgpu_reduce_uniform", type, op, target, source, nreduce, PE_start,
+                   logPE_stride, PE_size, pSync);
+}
+
+extern "C" int osgpu_has_reduce_uniform(int type, int op)
+{
+    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
 }

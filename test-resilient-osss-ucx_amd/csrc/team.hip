@@ -808,4 +808,206 @@ hipError_t launch_team_scan(int type, int op, int exclusive, int P, void *const 
     });
 }
 
+// ----------------------------------------------------- uniform reduce-to-all
+// osgpu_reduce_uniform: every member receives the ONE ascending fold
+// srcs[0] op srcs[1] op ... op srcs[P-1] -- the last member's inclusive scan,
+// member 0's reduce-to-all -- so all P targets hold the same bytes.  The same
+// owner-computes shape and the same 2*P*s HBM bytes per element as above.
+//
+// The scan kernel lets wave q refold inputs 0..q from LDS: P (P - 1) / 2
+// wave-level folds per 64 vectors (VALU issue is per wave whatever the lane
+// mask).  Here a tile is P sub-tiles of 64 vectors per member and each
+// sub-tile is folded ONCE:
+//   stage  wave p streams member p's P*64 vectors into LDS, its P loads in
+//          flight before the first LDS write (one read stream per wave);
+//   fold   wave w folds sub-tile w, one vector per lane, the P inputs read
+//          from LDS ascending; the result overwrites row 0 of sub-tile w,
+//          which no other wave reads;
+//   write  wave w streams the tile's P*64 result vectors (row 0) to member
+//          w's target (one write stream per wave).
+// LDS: P * P * 64 * 16 B = P^2 KiB a workgroup, 64 KiB at 8 members.  Every
+// wave reaches both barriers whatever part of the tile lies beyond nvec: a
+// last tile of 65 vectors leaves waves 2..P-1 nothing to fold, yet they have
+// targets to write.
+
+// the one ascending fold of an element by the exact ops
+template <typename T, int OP, int P>
+__device__ __forceinline__ T uniform_elem(const T (&x)[P])
+{
+    T acc = x[0];
+#pragma unroll
+    for (int p = 1; p < P; p++) acc = Elem<T, OP>::f(acc, x[p]);
+    return acc;
+}
+
+constexpr int kUniformSub = 64;  // vectors per sub-tile: one per lane of the folding wave
+
+template <typename T, int OP, int P>
+__global__ __launch_bounds__(64 * P) void team_uniform_lds_kernel(TeamPtrs<T, P> a, size_t nvec,
+                                                                  size_t head, size_t tail_start,
+                                                                  int nedge)
+{
+    constexpr int W = 16 / sizeof(T);
+    constexpr int V = kUniformSub * P;  // vectors per member per tile
+    __shared__ u32x4 tile[P][V];
+    if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
+        const size_t e = edge_index(head, tail_start);
+        T x[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) x[p] = a.src[p][e];
+        const T r = uniform_elem<T, OP, P>(x);
+#pragma unroll
+        for (int p = 0; p < P; p++) a.dst[p][e] = r;
+    }
+    // the member this wave stages and writes, the sub-tile it folds
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63);
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(pick(a.src, w) + head);
+    u32x4 *dst = reinterpret_cast<u32x4 *>(pick(a.dst, w) + head);
+    const size_t base = (size_t) blockIdx.x * V;
+    const bool whole = base + V <= nvec;
+    // (a branch per load would merge the P vectors at every join: 229 VGPRs
+    // at 8 members.)  A partial tile loads vector min(j, nvec - 1) in place of
+    // a vector j beyond nvec -- inside the array, never folded -- so its P
+    // loads are unconditional too; no tile starts at or beyond nvec but the
+    // one of a call without whole vectors, which loads nothing.
+    if (whole || base < nvec) {
+        const size_t last = nvec - 1 - base;  // of this tile's vectors, when partial
+        u32x4 v[P];
+#pragma unroll
+        for (int u = 0; u < P; u++) {
+            const size_t j = (size_t) (u * kUniformSub + lane);
+            v[u] = __builtin_nontemporal_load(src + base + (whole || j < last ? j : last));
+        }
+#pragma unroll
+        for (int u = 0; u < P; u++) tile[w][u * kUniformSub + lane] = v[u];
+    }
+    __syncthreads();
+    const int mine = w * kUniformSub + lane;
+    if (whole || base + mine < nvec) {
+        using F = Fast<T, OP>;
+        Vec16<T> in[P], out;
+#pragma unroll
+        for (int p = 0; p < P; p++) in[p].v = tile[p][mine];
+        // the branch-free fold first, the exact one only for a vector whose
+        // result holds a NaN part (elem_ops.hpp Fast)
+        bool bad = false;
+#pragma unroll
+        for (int e = 0; e < W; e++) {
+            T acc = in[0].e[e];
+#pragma unroll
+            for (int k = 1; k < P; k++) acc = F::f(acc, in[k].e[e]);
+            out.e[e] = acc;
+            bad = bad || F::bad(acc);
+        }
+        if (F::kChecked && __builtin_expect(bad, 0)) {
+#pragma unroll
+            for (int e = 0; e < W; e++) {
+                T acc = in[0].e[e];
+#pragma unroll
+                for (int k = 1; k < P; k++) acc = Elem<T, OP>::f(acc, in[k].e[e]);
+                out.e[e] = acc;
+            }
+        }
+        tile[0][mine] = out.v;
+    }
+    __syncthreads();
+    if (whole) {
+        u32x4 r[P];
+#pragma unroll
+        for (int u = 0; u < P; u++) r[u] = tile[0][u * kUniformSub + lane];
+#pragma unroll
+        for (int u = 0; u < P; u++)
+            __builtin_nontemporal_store(r[u], dst + base + u * kUniformSub + lane);
+        return;
+    }
+#pragma unroll
+    for (int u = 0; u < P; u++)
+        if (base + u * kUniformSub + lane < nvec)
+            __builtin_nontemporal_store(tile[0][u * kUniformSub + lane],
+                                        dst + base + u * kUniformSub + lane);
+}
+
+// element-granular form (pointers whose 16-byte phases differ): np members
+// of a table sized for kMaxTeam, so one instantiation serves every P
+template <typename T, int OP>
+__global__ __launch_bounds__(kTeamBlock) void team_uniform_scalar_kernel(TeamPtrs<T, kMaxTeam> a,
+                                                                         int np, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * kTeamBlock;
+    for (size_t i = (size_t) blockIdx.x * kTeamBlock + threadIdx.x; i < n; i += stride) {
+        T acc = a.src[0][i];
+#pragma unroll
+        for (int p = 1; p < kMaxTeam; p++)
+            if (p < np) acc = Elem<T, OP>::f(acc, a.src[p][i]);
+#pragma unroll
+        for (int q = 0; q < kMaxTeam; q++)
+            if (q < np) a.dst[q][i] = acc;
+    }
+}
+
+template <typename T, int OP, int P>
+static hipError_t uniform_launch_p(void *const *dsts, const void *const *srcs, const VecSplit &vs,
+                                   hipStream_t s)
+{
+    constexpr int W = 16 / sizeof(T);
+    constexpr size_t V = (size_t) kUniformSub * P;
+    // one tile per workgroup of P waves, in runs below the launch limit
+    // (for_each_tile_run): the first launch takes the edges, the others
+    // shifted pointers
+    return for_each_tile_run(vs.nvec, V, 64 * P, 1, [&](size_t t0, size_t nt, size_t nv) {
+        const size_t off = t0 == 0 ? 0 : vs.head + t0 * V * W;
+        TeamPtrs<T, P> a;
+        for (int p = 0; p < P; p++) {
+            a.src[p] = static_cast<const T *>(srcs[p]) + off;
+            a.dst[p] = static_cast<T *>(dsts[p]) + off;
+        }
+        hipLaunchKernelGGL((team_uniform_lds_kernel<T, OP, P>), dim3((unsigned) nt), dim3(64 * P),
+                           0, s, a, nv, t0 == 0 ? vs.head : (size_t) 0,
+                           t0 == 0 ? vs.tail_start : (size_t) 0, t0 == 0 ? vs.nedge : 0);
+        return hipGetLastError();
+    });
+}
+
+template <typename T, int OP>
+static hipError_t uniform_launch_op(int P, void *const *d, const void *const *sr, size_t n,
+                                    hipStream_t s)
+{
+    const VecSplit vs = vec_split(sizeof(T), n, sr, P, d, P);
+    if (!vs.vec) {
+        TeamPtrs<T, kMaxTeam> a;
+        for (int p = 0; p < kMaxTeam; p++) {
+            a.src[p] = p < P ? static_cast<const T *>(sr[p]) : nullptr;
+            a.dst[p] = p < P ? static_cast<T *>(d[p]) : nullptr;
+        }
+        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
+        blocks = blocks > 8192 ? 8192 : blocks;
+        hipLaunchKernelGGL((team_uniform_scalar_kernel<T, OP>), dim3((unsigned) blocks),
+                           dim3(kTeamBlock), 0, s, a, P, n);
+        return hipGetLastError();
+    }
+    switch (P) {
+    case 2: return uniform_launch_p<T, OP, 2>(d, sr, vs, s);
+    case 3: return uniform_launch_p<T, OP, 3>(d, sr, vs, s);
+    case 4: return uniform_launch_p<T, OP, 4>(d, sr, vs, s);
+    case 5: return uniform_launch_p<T, OP, 5>(d, sr, vs, s);
+    case 6: return uniform_launch_p<T, OP, 6>(d, sr, vs, s);
+    case 7: return uniform_launch_p<T, OP, 7>(d, sr, vs, s);
+    case 8: return uniform_launch_p<T, OP, 8>(d, sr, vs, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_team_uniform(int type, int op, int P, void *const *dsts, const void *const *srcs,
+                               size_t n, hipStream_t s)
+{
+    if (P < 2 || P > kMaxTeam) return hipErrorInvalidValue;
+    if (type == T_LONGDOUBLE) return launch_uniform_longdouble(op, P, dsts, srcs, n, s);
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        if (n == 0) return hipSuccess;
+        return uniform_launch_op<typename decltype(t)::type, decltype(o)::value>(P, dsts, srcs, n,
+                                                                                 s);
+    });
+}
+
 }  // namespace osgpu

@@ -166,6 +166,10 @@ def load() -> ctypes.CDLL:
     L.osgpu_has_scan.argtypes = [i, i]
     L.osgpu_scan_identity.argtypes = [i, i, vp]
     L.osgpu_team_scan.argtypes = [i, i, i, i, vp, vp, sz, vp]
+    L.osgpu_reduce_uniform.argtypes = [i, i, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_reduce_uniform.restype = None
+    L.osgpu_has_reduce_uniform.argtypes = [i, i]
+    L.osgpu_team_uniform.argtypes = [i, i, i, vp, vp, sz, vp]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -452,6 +456,29 @@ def team_scan(t: str, op: str, exclusive: bool, dsts, srcs, n: int, stream: int 
                            (ctypes.c_void_p * P)(*dsts), (ctypes.c_void_p * P)(*srcs), n, stream)
     if rc != 0 and check:
         raise RuntimeError(f"osgpu_team_scan({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
+
+
+def reduce_uniform(t: str, op: str):
+    """osgpu_reduce_uniform bound to the codes of (t, op): a function with the
+    arguments of shmem_<t>_<op>_to_all (target, source, nreduce, PE_start,
+    logPE_stride, PE_size, pWrk, pSync); every member receives the one
+    ascending fold of all members' sources, the same bytes."""
+    f, tc, oc = load().osgpu_reduce_uniform, type_code(t), OPS.index(op)
+    return lambda *args: f(tc, oc, *args)
+
+
+def team_uniform(t: str, op: str, dsts, srcs, n: int, stream: int | None = None,
+                 check: bool = True) -> int:
+    """Enqueue the owner-computes uniform kernel: every dsts[q] = srcs[0] op
+    ... op srcs[P-1] (device ptrs).  Returns the status; check=True raises on
+    a non-zero one."""
+    L = load()
+    P = len(srcs)
+    rc = L.osgpu_team_uniform(type_code(t), OPS.index(op), P, (ctypes.c_void_p * P)(*dsts),
+                              (ctypes.c_void_p * P)(*srcs), n, stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_team_uniform({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
     return rc
 
 
