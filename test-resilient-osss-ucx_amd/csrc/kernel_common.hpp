@@ -2,7 +2,7 @@
 // included by the host .cpp layer.
 //  * u32x4 / Vec16: the 16-byte vector a lane loads and stores;
 //  * dispatch_type_op: which (type, op) pairs exist and the C++ type of each
-//    type code;
+//    type code; dispatch_members: the member counts a team kernel is built for;
 //  * vec_split / edge_index: n elements at a 16-byte phase as a scalar head,
 //    whole vectors and a scalar tail;
 //  * for_each_tile_run: a call of more than max_launch_threads() threads as
@@ -83,6 +83,24 @@ template <typename R, typename F>
 R dispatch_ld_op(int op, R fallback, F &&f)
 {
     return dispatch_op<long double>(op, fallback, [&](auto, auto o) { return f(o); });
+}
+
+// f(integral_constant<int, P>) for the member counts the team kernels are
+// built for, 2 .. kMaxTeam; else fallback
+template <typename R, typename F>
+R dispatch_members(int P, R fallback, F &&f)
+{
+    static_assert(kMaxTeam == 8, "one case per member count");
+    switch (P) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    }
+    return fallback;
 }
 
 // ------------------------------------------------------------ vector split

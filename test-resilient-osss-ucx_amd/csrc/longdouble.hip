@@ -237,18 +237,14 @@ template <int OP>
 hipError_t ld_team_launch(int P, bool vec, const LdTeam &a, size_t n, unsigned blocks,
                           hipStream_t s)
 {
-    switch (P) {
-#define LDT(PP)                                                                \
-    case PP:                                                                   \
-        if (vec)                                                               \
-            hipLaunchKernelGGL((ld_team_kernel<OP, PP, true>), dim3(blocks), dim3(256), 0, s, a, n); \
-        else                                                                   \
-            hipLaunchKernelGGL((ld_team_kernel<OP, PP, false>), dim3(blocks), dim3(256), 0, s, a, n); \
+    return dispatch_members(P, hipErrorInvalidValue, [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        if (vec)
+            hipLaunchKernelGGL((ld_team_kernel<OP, PP, true>), dim3(blocks), dim3(256), 0, s, a, n);
+        else
+            hipLaunchKernelGGL((ld_team_kernel<OP, PP, false>), dim3(blocks), dim3(256), 0, s, a, n);
         return hipGetLastError();
-        LDT(2) LDT(3) LDT(4) LDT(5) LDT(6) LDT(7) LDT(8)
-#undef LDT
-    }
-    return hipErrorInvalidValue;
+    });
 }
 
 }  // namespace x87
@@ -306,18 +302,14 @@ template <int OP>
 hipError_t ld_uniform_launch(int P, bool vec, const LdTeam &a, size_t n, unsigned blocks,
                              hipStream_t s)
 {
-    switch (P) {
-#define LDU(PP)                                                                \
-    case PP:                                                                   \
-        if (vec)                                                               \
-            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, true>), dim3(blocks), dim3(256), 0, s, a, n); \
-        else                                                                   \
-            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, false>), dim3(blocks), dim3(256), 0, s, a, n); \
+    return dispatch_members(P, hipErrorInvalidValue, [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        if (vec)
+            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, true>), dim3(blocks), dim3(256), 0, s, a, n);
+        else
+            hipLaunchKernelGGL((ld_uniform_kernel<OP, PP, false>), dim3(blocks), dim3(256), 0, s, a, n);
         return hipGetLastError();
-        LDU(2) LDU(3) LDU(4) LDU(5) LDU(6) LDU(7) LDU(8)
-#undef LDU
-    }
-    return hipErrorInvalidValue;
+    });
 }
 
 }  // namespace x87

@@ -1177,11 +1177,13 @@ void zero_ld_padding(const Call &c, void *p)
     for (size_t i = 0; i < (size_t) c.nreduce; i++) memset((char *) p + 16 * i + 10, 0, 6);
 }
 
-// TEAM: every member launches the scan kernel over its own contiguous shard
-// of all P targets, between the two barriers.  (No tiles / merge scheme of
-// local members: run_team's bookkeeping is the reduce-to-all's.)
-void run_scan_team(const Call &c, int excl, const std::vector<const void *> &srcs,
-                   const std::vector<void *> &dsts, int idx)
+// TEAM of the scan and the uniform reduce (`what`): every member launches the
+// kernel, launch(P, dsts, srcs, n, stream), over its own contiguous shard of
+// all P targets, between the two barriers.  (No tiles / merge scheme of local
+// members: run_team's bookkeeping is the reduce-to-all's.)
+template <class Launch>
+void run_team_shards(const Call &c, const std::vector<const void *> &srcs,
+                     const std::vector<void *> &dsts, int idx, const char *what, Launch launch)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
@@ -1197,12 +1199,8 @@ void run_scan_team(const Call &c, int excl, const std::vector<const void *> &src
         sp[i] = (const char *) srcs[i] + (size_t) lo * s;
         dp[i] = (char *) dsts[i] + (size_t) lo * s;
     }
-    DBG("%s PE %d: team scan, [%lld, %lld) of %d, P=%d, exclusive %d", c.name, c.me, lo, hi,
-        c.nreduce, P, excl);
-    if (hi > lo)
-        launched(c.name, "team scan launch",
-                 osgpu::launch_team_scan(c.type, c.op, excl, P, dp.data(), sp.data(),
-                                         (size_t) (hi - lo), st));
+    DBG("%s PE %d: %s, [%lld, %lld) of %d, P=%d", c.name, c.me, what, lo, hi, c.nreduce, P);
+    if (hi > lo) launched(c.name, what, launch(P, dp.data(), sp.data(), (size_t) (hi - lo), st));
     stream_wait(c.name, st);
     barrier(c);  // every shard of my target is written
 }
@@ -1393,7 +1391,10 @@ void scan(const char *name, int type, int op, int exclusive, void *target, const
     // and more than 8 members take the pull form
     if (path_mode() != OSGPU_PATH_PULL && type != OSGPU_T_LONGDOUBLE &&
         (idx = team_ptrs(c, srcs, dsts)) >= 0)
-        run_scan_team(c, exclusive, srcs, dsts, idx);
+        run_team_shards(c, srcs, dsts, idx, exclusive ? "team exclusive scan" : "team inclusive scan",
+                        [&](int P, void *const *d, const void *const *sr, size_t n, hipStream_t st) {
+                            return osgpu::launch_team_scan(type, op, exclusive, P, d, sr, n, st);
+                        });
     else
         run_scan_pull(c, exclusive);
 }
@@ -1407,34 +1408,6 @@ void scan(const char *name, int type, int op, int exclusive, void *target, const
 // included) or the pull form; host heaps the host fold and GETMEM.  The pull
 // and host forms are the scan's over K = PE_size members: never
 // osgpu_fold_order's caller-first order.  No FUSED, STAGED, RCCL or push form.
-
-// TEAM: every member launches the uniform kernel over its own contiguous
-// shard of all P targets, between the two barriers.
-void run_uniform_team(const Call &c, const std::vector<const void *> &srcs,
-                      const std::vector<void *> &dsts, int idx)
-{
-    hipStream_t st = pe_stream(c.name, c.me);
-    const size_t s = type_size(c.type);
-    const int P = c.PE_size;
-    t_last_path = OSGPU_RAN_TEAM;
-    entry_sync(c.name, st);
-    barrier(c);  // every source is ready, every target writable
-    long long lo = 0, hi = 0;
-    shard_of(c.nreduce, P, idx, s, &lo, &hi);
-    std::vector<const void *> sp(P);
-    std::vector<void *> dp(P);
-    for (int i = 0; i < P; i++) {
-        sp[i] = (const char *) srcs[i] + (size_t) lo * s;
-        dp[i] = (char *) dsts[i] + (size_t) lo * s;
-    }
-    DBG("%s PE %d: team uniform, [%lld, %lld) of %d, P=%d", c.name, c.me, lo, hi, c.nreduce, P);
-    if (hi > lo)
-        launched(c.name, "team uniform launch",
-                 osgpu::launch_team_uniform(c.type, c.op, P, dp.data(), sp.data(),
-                                            (size_t) (hi - lo), st));
-    stream_wait(c.name, st);
-    barrier(c);  // every shard of my target is written
-}
 
 void run_uniform_pull(const Call &c) { run_prefix_pull(c, c.PE_size); }
 void run_uniform_host_fold(const Call &c) { run_prefix_host_fold(c, c.PE_size); }
@@ -1489,7 +1462,10 @@ void reduce_uniform(const char *name, int type, int op, void *target, const void
     // is not this one), for every type; an overlap, a target outside the
     // heaps, one member and more than 8 take the pull form
     if (path_mode() != OSGPU_PATH_PULL && (idx = team_ptrs(c, srcs, dsts)) >= 0)
-        run_uniform_team(c, srcs, dsts, idx);
+        run_team_shards(c, srcs, dsts, idx, "team uniform",
+                        [&](int P, void *const *d, const void *const *sr, size_t n, hipStream_t st) {
+                            return osgpu::launch_team_uniform(type, op, P, d, sr, n, st);
+                        });
     else
         run_uniform_pull(c);
 }

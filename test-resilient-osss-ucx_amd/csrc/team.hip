@@ -452,6 +452,55 @@ struct Tiles {
     }
 };
 
+// the callers' first np members, `off` elements in, as a table of N (the rest null)
+template <typename T, int N>
+static TeamPtrs<T, N> team_table(void *const *dsts, const void *const *srcs, int np, size_t off)
+{
+    TeamPtrs<T, N> a;
+    for (int p = 0; p < N; p++) {
+        a.src[p] = p < np ? static_cast<const T *>(srcs[p]) + off : nullptr;
+        a.dst[p] = p < np ? static_cast<T *>(dsts[p]) + off : nullptr;
+    }
+    return a;
+}
+
+// `kernel` (a, nvec, head, tail_start, nedge, tail...) over the vectors of
+// vs in tiles of V, this member's every tl.m-th one, one per workgroup of
+// `threads`, in runs that are whole multiples of tl.m (for_each_tile_run):
+// the first launch takes head, tail_start and the edges (member 0's first
+// workgroup folds them), the others zeros and pointers shifted to their
+// first tile.
+template <typename T, int P, typename Kernel, typename... Tail>
+static hipError_t launch_tile_runs(Kernel kernel, size_t V, unsigned threads, Tiles tl,
+                                   void *const *dsts, const void *const *srcs, const VecSplit &vs,
+                                   hipStream_t s, Tail... tail)
+{
+    constexpr int W = 16 / sizeof(T);
+    return for_each_tile_run(vs.nvec, V, threads, tl.m, [&](size_t t0, size_t nt, size_t nv) {
+        const bool first = t0 == 0;
+        const TeamPtrs<T, P> a = team_table<T, P>(dsts, srcs, P, first ? 0 : vs.head + t0 * V * W);
+        hipLaunchKernelGGL(kernel, dim3((unsigned) tl.blocks(nt)), dim3(threads), 0, s, a, nv,
+                           first ? vs.head : (size_t) 0, first ? vs.tail_start : (size_t) 0,
+                           first && tl.k == 0 ? vs.nedge : 0, tail...);
+        return hipGetLastError();
+    });
+}
+// the scan and the uniform reduce: every tile is this member's
+constexpr Tiles kAllTiles{1, 0, false};
+
+// `kernel` (a, np, n, tail...), element-granular over a table sized for
+// kMaxTeam (pointers whose 16-byte phases differ)
+template <typename T, typename Kernel, typename... Tail>
+static hipError_t launch_elem_table(Kernel kernel, int P, void *const *dsts,
+                                    const void *const *srcs, size_t n, hipStream_t s, Tail... tail)
+{
+    size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
+    blocks = blocks > 8192 ? 8192 : blocks;
+    hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(kTeamBlock), 0, s,
+                       (team_table<T, kMaxTeam>(dsts, srcs, P, 0)), P, n, tail...);
+    return hipGetLastError();
+}
+
 template <typename T, int OP, int P, bool REMOTE>
 static hipError_t team_launch_p(void *const *dsts, const void *const *srcs, size_t n,
                                 Tiles tl, hipStream_t s)
@@ -460,51 +509,23 @@ static hipError_t team_launch_p(void *const *dsts, const void *const *srcs, size
     // integer ops are order-independent (wrapping ring / lattice ops); every
     // floating-point op, min/max included (NaN, signed zero), is not
     constexpr bool ORDERED = !std::is_integral<T>::value;
-    TeamPtrs<T, P> a;
-    for (int p = 0; p < P; p++) {
-        a.src[p] = static_cast<const T *>(srcs[p]);
-        a.dst[p] = static_cast<T *>(dsts[p]);
-    }
     const VecSplit vs = vec_split(sizeof(T), n, srcs, P, dsts, P);
     if (!vs.vec) {
         size_t blocks = tl.blocks((n + kTeamBlock - 1) / kTeamBlock);
         blocks = blocks > 8192 ? 8192 : blocks;
         hipLaunchKernelGGL((team_scalar_kernel<T, OP, P, ORDERED>), dim3((unsigned) blocks),
-                           dim3(kTeamBlock), 0, s, a, n, tl.m, tl.k);
+                           dim3(kTeamBlock), 0, s, (team_table<T, P>(dsts, srcs, P, 0)), n, tl.m,
+                           tl.k);
         return hipGetLastError();
     }
-    constexpr int W = 16 / sizeof(T);
-    // the unaligned head and the tail: member 0's first workgroup
-    const int nedge = tl.k == 0 ? vs.nedge : 0;
-    // tiles of V vectors, this member's every tl.m-th one, one per workgroup
-    // of `threads`, in runs that are whole multiples of tl.m
-    // (for_each_tile_run): the first launch takes the edges, the others
-    // shifted pointers
-    auto launch = [&](size_t V, unsigned threads, auto kernel) -> hipError_t {
-        return for_each_tile_run(vs.nvec, V, threads, tl.m, [&](size_t t0, size_t nt, size_t nv) {
-            const size_t blocks = tl.blocks(nt);
-            if (t0 == 0) {
-                hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, s, a, nv,
-                                   vs.head, vs.tail_start, nedge, tl.m, tl.k);
-            } else {
-                const size_t off = vs.head + t0 * V * W;
-                TeamPtrs<T, P> c;
-                for (int p = 0; p < P; p++) {
-                    c.src[p] = a.src[p] + off;
-                    c.dst[p] = a.dst[p] + off;
-                }
-                hipLaunchKernelGGL(kernel, dim3((unsigned) blocks), dim3(threads), 0, s, c, nv,
-                                   (size_t) 0, (size_t) 0, 0, tl.m, tl.k);
-            }
-            return hipGetLastError();
-        });
-    };
     if constexpr (S::kLds) {
         constexpr int UL = S::kLdsU;
-        return launch((size_t) 64 * UL, 64 * P, team_lds_kernel<T, OP, P, ORDERED, UL>);
+        return launch_tile_runs<T, P>(team_lds_kernel<T, OP, P, ORDERED, UL>, (size_t) 64 * UL,
+                                      64 * P, tl, dsts, srcs, vs, s, tl.m, tl.k);
     } else {  // (not instantiated where the LDS form is used)
-        return launch((size_t) kTeamBlock * S::U, kTeamBlock,
-                      team_vec_kernel<T, OP, P, ORDERED, REMOTE>);
+        return launch_tile_runs<T, P>(team_vec_kernel<T, OP, P, ORDERED, REMOTE>,
+                                      (size_t) kTeamBlock * S::U, kTeamBlock, tl, dsts, srcs, vs,
+                                      s, tl.m, tl.k);
     }
 }
 
@@ -522,16 +543,9 @@ template <typename T, int OP>
 static hipError_t team_launch_op(int P, void *const *d, const void *const *sr, size_t n,
                                  Tiles tl, hipStream_t s)
 {
-    switch (P) {
-    case 2: return team_launch_pr<T, OP, 2>(d, sr, n, tl, s);
-    case 3: return team_launch_pr<T, OP, 3>(d, sr, n, tl, s);
-    case 4: return team_launch_pr<T, OP, 4>(d, sr, n, tl, s);
-    case 5: return team_launch_pr<T, OP, 5>(d, sr, n, tl, s);
-    case 6: return team_launch_pr<T, OP, 6>(d, sr, n, tl, s);
-    case 7: return team_launch_pr<T, OP, 7>(d, sr, n, tl, s);
-    case 8: return team_launch_pr<T, OP, 8>(d, sr, n, tl, s);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_members(P, hipErrorInvalidValue, [&](auto pc) {
+        return team_launch_pr<T, OP, decltype(pc)::value>(d, sr, n, tl, s);
+    });
 }
 
 hipError_t launch_team_tiles(int type, int op, int P, void *const *dsts, const void *const *srcs,
@@ -738,58 +752,19 @@ hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s
     return hipGetLastError();
 }
 
-template <typename T, int OP, int P>
-static hipError_t scan_launch_p(void *const *dsts, const void *const *srcs, const VecSplit &vs,
-                                int excl, u32x4 ident, hipStream_t s)
-{
-    constexpr int W = 16 / sizeof(T);
-    constexpr int UL = OSGPU_TEAM_LDS_U;
-    constexpr size_t V = (size_t) 64 * UL;
-    // one tile per workgroup of P waves, in runs below the launch limit
-    // (for_each_tile_run): the first launch takes the edges, the others
-    // shifted pointers
-    return for_each_tile_run(vs.nvec, V, 64 * P, 1, [&](size_t t0, size_t nt, size_t nv) {
-        const size_t off = t0 == 0 ? 0 : vs.head + t0 * V * W;
-        TeamPtrs<T, P> a;
-        for (int p = 0; p < P; p++) {
-            a.src[p] = static_cast<const T *>(srcs[p]) + off;
-            a.dst[p] = static_cast<T *>(dsts[p]) + off;
-        }
-        hipLaunchKernelGGL((team_scan_lds_kernel<T, OP, P, UL>), dim3((unsigned) nt),
-                           dim3(64 * P), 0, s, a, nv, t0 == 0 ? vs.head : (size_t) 0,
-                           t0 == 0 ? vs.tail_start : (size_t) 0, t0 == 0 ? vs.nedge : 0, excl,
-                           ident);
-        return hipGetLastError();
-    });
-}
-
 template <typename T, int OP>
 static hipError_t scan_launch_op(int P, void *const *d, const void *const *sr, size_t n, int excl,
                                  u32x4 ident, hipStream_t s)
 {
     const VecSplit vs = vec_split(sizeof(T), n, sr, P, d, P);
-    if (!vs.vec) {
-        TeamPtrs<T, kMaxTeam> a;
-        for (int p = 0; p < kMaxTeam; p++) {
-            a.src[p] = p < P ? static_cast<const T *>(sr[p]) : nullptr;
-            a.dst[p] = p < P ? static_cast<T *>(d[p]) : nullptr;
-        }
-        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
-        blocks = blocks > 8192 ? 8192 : blocks;
-        hipLaunchKernelGGL((team_scan_scalar_kernel<T, OP>), dim3((unsigned) blocks),
-                           dim3(kTeamBlock), 0, s, a, P, n, excl, ident);
-        return hipGetLastError();
-    }
-    switch (P) {
-    case 2: return scan_launch_p<T, OP, 2>(d, sr, vs, excl, ident, s);
-    case 3: return scan_launch_p<T, OP, 3>(d, sr, vs, excl, ident, s);
-    case 4: return scan_launch_p<T, OP, 4>(d, sr, vs, excl, ident, s);
-    case 5: return scan_launch_p<T, OP, 5>(d, sr, vs, excl, ident, s);
-    case 6: return scan_launch_p<T, OP, 6>(d, sr, vs, excl, ident, s);
-    case 7: return scan_launch_p<T, OP, 7>(d, sr, vs, excl, ident, s);
-    case 8: return scan_launch_p<T, OP, 8>(d, sr, vs, excl, ident, s);
-    }
-    return hipErrorInvalidValue;
+    if (!vs.vec)
+        return launch_elem_table<T>(team_scan_scalar_kernel<T, OP>, P, d, sr, n, s, excl, ident);
+    return dispatch_members(P, hipErrorInvalidValue, [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        constexpr int UL = OSGPU_TEAM_LDS_U;
+        return launch_tile_runs<T, PP>(team_scan_lds_kernel<T, OP, PP, UL>, (size_t) 64 * UL,
+                                       64 * PP, kAllTiles, d, sr, vs, s, excl, ident);
+    });
 }
 
 hipError_t launch_team_scan(int type, int op, int exclusive, int P, void *const *dsts,
@@ -946,56 +921,17 @@ __global__ __launch_bounds__(kTeamBlock) void team_uniform_scalar_kernel(TeamPtr
     }
 }
 
-template <typename T, int OP, int P>
-static hipError_t uniform_launch_p(void *const *dsts, const void *const *srcs, const VecSplit &vs,
-                                   hipStream_t s)
-{
-    constexpr int W = 16 / sizeof(T);
-    constexpr size_t V = (size_t) kUniformSub * P;
-    // one tile per workgroup of P waves, in runs below the launch limit
-    // (for_each_tile_run): the first launch takes the edges, the others
-    // shifted pointers
-    return for_each_tile_run(vs.nvec, V, 64 * P, 1, [&](size_t t0, size_t nt, size_t nv) {
-        const size_t off = t0 == 0 ? 0 : vs.head + t0 * V * W;
-        TeamPtrs<T, P> a;
-        for (int p = 0; p < P; p++) {
-            a.src[p] = static_cast<const T *>(srcs[p]) + off;
-            a.dst[p] = static_cast<T *>(dsts[p]) + off;
-        }
-        hipLaunchKernelGGL((team_uniform_lds_kernel<T, OP, P>), dim3((unsigned) nt), dim3(64 * P),
-                           0, s, a, nv, t0 == 0 ? vs.head : (size_t) 0,
-                           t0 == 0 ? vs.tail_start : (size_t) 0, t0 == 0 ? vs.nedge : 0);
-        return hipGetLastError();
-    });
-}
-
 template <typename T, int OP>
 static hipError_t uniform_launch_op(int P, void *const *d, const void *const *sr, size_t n,
                                     hipStream_t s)
 {
     const VecSplit vs = vec_split(sizeof(T), n, sr, P, d, P);
-    if (!vs.vec) {
-        TeamPtrs<T, kMaxTeam> a;
-        for (int p = 0; p < kMaxTeam; p++) {
-            a.src[p] = p < P ? static_cast<const T *>(sr[p]) : nullptr;
-            a.dst[p] = p < P ? static_cast<T *>(d[p]) : nullptr;
-        }
-        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
-        blocks = blocks > 8192 ? 8192 : blocks;
-        hipLaunchKernelGGL((team_uniform_scalar_kernel<T, OP>), dim3((unsigned) blocks),
-                           dim3(kTeamBlock), 0, s, a, P, n);
-        return hipGetLastError();
-    }
-    switch (P) {
-    case 2: return uniform_launch_p<T, OP, 2>(d, sr, vs, s);
-    case 3: return uniform_launch_p<T, OP, 3>(d, sr, vs, s);
-    case 4: return uniform_launch_p<T, OP, 4>(d, sr, vs, s);
-    case 5: return uniform_launch_p<T, OP, 5>(d, sr, vs, s);
-    case 6: return uniform_launch_p<T, OP, 6>(d, sr, vs, s);
-    case 7: return uniform_launch_p<T, OP, 7>(d, sr, vs, s);
-    case 8: return uniform_launch_p<T, OP, 8>(d, sr, vs, s);
-    }
-    return hipErrorInvalidValue;
+    if (!vs.vec) return launch_elem_table<T>(team_uniform_scalar_kernel<T, OP>, P, d, sr, n, s);
+    return dispatch_members(P, hipErrorInvalidValue, [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        return launch_tile_runs<T, PP>(team_uniform_lds_kernel<T, OP, PP>,
+                                       (size_t) kUniformSub * PP, 64 * PP, kAllTiles, d, sr, vs, s);
+    });
 }
 
 hipError_t launch_team_uniform(int type, int op, int P, void *const *dsts, const void *const *srcs,
