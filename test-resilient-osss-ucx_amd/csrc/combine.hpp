@@ -104,6 +104,21 @@ hipError_t launch_team_uniform(int type, int op, int P, void *const *dsts,
                                const void *const *srcs, size_t n, hipStream_t s);
 hipError_t launch_uniform_longdouble(int op, int P, void *const *dsts, const void *const *srcs,
                                      size_t n, hipStream_t s);
+// Max / min with location (team.hip): for i < n and every q < ndst,
+// (val_dsts[q][i], loc_dsts[q][i]) = the ascending fold of the P pairs
+// (val_srcs[p][i], loc_srcs[p][i]) by elem_ops.hpp LocStep; op OP_MAX or
+// OP_MIN, the ordered types but long double.  1 <= P <= 8; ndst is 1 or P.
+// loc_srcs null: member p's elements all carry member_locs[p] (a host array,
+// passed to the kernel by value).  loc_srcs[0] set and loc_srcs[1] null
+// (P > 1): input 0 alone has an index stream, the others member_locs[p] --
+// a later chunk of a fold over more than 8 inputs, whose input 0 is the pair
+// folded so far; a destination may then be input 0 itself (every element is
+// read and written by one lane).  Otherwise targets must not overlap sources.
+// Multi-launch above max_launch_threads().
+hipError_t launch_team_loc(int type, int op, int P, int ndst, void *const *val_dsts,
+                           int *const *loc_dsts, const void *const *val_srcs,
+                           const int *const *loc_srcs, const int *member_locs, size_t n,
+                           hipStream_t s);
 // n elements of the identity of (type, op) (scan_host.hpp scan_identity) at
 // dst, any alignment; long double's padding bytes zero (team.hip)
 hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s);
@@ -142,6 +157,12 @@ bool set_strided_shape(int form, int u, int nt);
 // in[i]) for i < n with the kernels' element ops compiled for the host
 bool host_fold_supported(int type, int op);
 bool host_fold(int type, int op, void *acc, const void *in, size_t n);
+// The same for osgpu_reduce_loc: (val[k], loc[k]) takes (in_val[k], in_loc ?
+// in_loc[k] : in_const) by elem_ops.hpp LocStep; max / min of the ordered
+// types but long double
+bool host_fold_loc_supported(int type, int op);
+bool host_fold_loc(int type, int op, void *val, int *loc, const void *in_val, const int *in_loc,
+                   int in_const, size_t n);
 // One range between HBM and pinned host memory mapped into the GPU (either
 // side may be the host's device view): a fixed grid (OSGPU_HOST_COPY_GRID,
 // default 256 workgroups) sized for one PCIe link, not for HBM (copy.hip)

@@ -288,6 +288,15 @@ OSGPU_EHD H arith16(H a, H b)
 }
 OSGPU_EHD bool gt16(bf16_t a, bf16_t b) { return widen(a) > widen(b); }
 OSGPU_EHD bool lt16(bf16_t a, bf16_t b) { return widen(a) < widen(b); }
+OSGPU_EHD bool eq16(bf16_t a, bf16_t b) { return widen(a) == widen(b); }
+#if defined(__HIP_DEVICE_COMPILE__)
+OSGPU_EHD bool eq16(half_t a, half_t b)
+{
+    return __builtin_bit_cast(_Float16, a.u) == __builtin_bit_cast(_Float16, b.u);
+}
+#else
+OSGPU_EHD bool eq16(half_t a, half_t b) { return widen(a) == widen(b); }
+#endif
 #if defined(__HIP_DEVICE_COMPILE__)
 OSGPU_EHD bool gt16(half_t a, half_t b)
 {
@@ -321,6 +330,37 @@ template <> struct Elem<bf16_t, OP_SUM> : Elem16<bf16_t, OP_SUM> {};
 template <> struct Elem<bf16_t, OP_PROD> : Elem16<bf16_t, OP_PROD> {};
 template <> struct Elem<bf16_t, OP_MAX> : Elem16<bf16_t, OP_MAX> {};
 template <> struct Elem<bf16_t, OP_MIN> : Elem16<bf16_t, OP_MIN> {};
+
+// ------------------------------------------------ max / min with location
+// One step of osgpu_reduce_loc's ascending fold (OP_MAX / OP_MIN over the
+// ordered types): the running pair (v, i) takes member j's pair (b, ib).
+//   v before b (v > b for max, v < b for min): (v, i) stays;
+//   v == b:  v becomes b -- what Elem<T, OP>::f returns -- and i = min(i, ib);
+//   else (b before v, or unordered): (b, ib).
+// Comparisons are on values: a NaN compares false both ways, so it replaces
+// what came before it and is replaced by what comes after it; +0 == -0.  The
+// value part IS Elem<T, OP>::f, so the values are the uniform reduce's bits.
+// Indices compare as signed 32-bit integers.
+template <typename T, int OP> struct LocStep {
+    static_assert(OP == OP_MAX || OP == OP_MIN, "max / min only");
+    OSGPU_EHD static bool before(T a, T b)
+    {
+        if constexpr (is_f16<T>::value) return OP == OP_MAX ? gt16(a, b) : lt16(a, b);
+        else return OP == OP_MAX ? a > b : a < b;
+    }
+    OSGPU_EHD static bool same(T a, T b)
+    {
+        if constexpr (is_f16<T>::value) return eq16(a, b);
+        else return a == b;
+    }
+    OSGPU_EHD static void f(T &v, int32_t &i, T b, int32_t ib)
+    {
+        const bool keep = before(v, b), tie = same(v, b);
+        const int32_t lo = i < ib ? i : ib;
+        i = keep ? i : (tie ? lo : ib);
+        v = Elem<T, OP>::f(v, b);
+    }
+};
 
 // ------------------------------------------------------- branch-free folds
 // Fast<T, OP>::f is Elem<T, OP>::f without its NaN handling (the SSE rule,

@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "kernel_common.hpp"
+#include "loc_host.hpp"
 #include "x87.hpp"
 
 #pragma clang fp contract(off)
@@ -71,7 +72,41 @@ FoldFn fold_fn(int type, int op)
     });
 }
 
+typedef void (*LocFoldFn)(void *, int32_t *, const void *, const int32_t *, int32_t, size_t);
+
+// osgpu_reduce_loc's step (elem_ops.hpp LocStep) over loc_host.hpp's loop
+template <typename T, int OP>
+void fold_loc_n(void *v, int32_t *i, const void *b, const int32_t *ib, int32_t ib_const, size_t n)
+{
+    rt::loc_fold_n<LocStep<T, OP>, T>(static_cast<T *>(v), i, static_cast<const T *>(b), ib,
+                                      ib_const, n);
+}
+
+LocFoldFn loc_fold_fn(int type, int op)
+{
+    return dispatch_type_op(type, op, (LocFoldFn) nullptr, [](auto t, auto o) -> LocFoldFn {
+        using T = typename decltype(t)::type;
+        constexpr int OP = decltype(o)::value;
+        constexpr bool kOrdered = std::is_integral<T>::value || std::is_floating_point<T>::value ||
+                                  is_f16<T>::value;
+        if constexpr (kOrdered && (OP == OP_MAX || OP == OP_MIN)) return fold_loc_n<T, OP>;
+        else return nullptr;
+    });
+}
+
 }  // namespace
+
+bool host_fold_loc_supported(int type, int op) { return loc_fold_fn(type, op) != nullptr; }
+
+// (val[k], loc[k]) takes (in_val[k], in_loc ? in_loc[k] : in_const) for k < n
+bool host_fold_loc(int type, int op, void *val, int *loc, const void *in_val, const int *in_loc,
+                   int in_const, size_t n)
+{
+    const LocFoldFn f = loc_fold_fn(type, op);
+    if (!f) return false;
+    f(val, loc, in_val, in_loc, in_const, n);
+    return true;
+}
 
 bool host_fold_supported(int type, int op) { return fold_fn(type, op) != nullptr; }
 

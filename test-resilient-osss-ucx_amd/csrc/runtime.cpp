@@ -25,6 +25,7 @@
 
 #include "../../include/osgpu_reduce.h"
 #include "combine.hpp"
+#include "loc_host.hpp"
 #include "psync_board.hpp"
 #include "runtime.hpp"
 
@@ -1639,6 +1640,28 @@ int osgpu_team_uniform(int type, int op, int P, void *const *dsts, const void *c
     hipError_t e = osgpu::launch_team_uniform(type, op, P, dsts, srcs, nelems, st);
     if (e != hipSuccess) {
         set_err("osgpu_team_uniform: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
+int osgpu_team_loc(int type, int op, int P, int ndst, void *const *val_dsts, int *const *loc_dsts,
+                   const void *const *val_srcs, const int *const *loc_srcs,
+                   const int *member_locs, size_t nelems, void *hip_stream)
+{
+    bool ok = osgpu::rt::loc_pair(type, op) && P >= 1 && P <= osgpu::kMaxTeam &&
+              (ndst == 1 || ndst == P) && val_dsts && loc_dsts && val_srcs &&
+              (loc_srcs || member_locs);
+    for (int p = 0; ok && loc_srcs && p < P; p++) ok = loc_srcs[p] != nullptr;
+    if (!ok) {
+        set_err("osgpu_team_loc: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_team_loc");
+    hipError_t e = osgpu::launch_team_loc(type, op, P, ndst, val_dsts, loc_dsts, val_srcs, loc_srcs,
+                                          member_locs, nelems, st);
+    if (e != hipSuccess) {
+        set_err("osgpu_team_loc: %s", hipGetErrorString(e));
         return OSGPU_EHIP;
     }
     return OSGPU_OK;

@@ -40,6 +40,7 @@
 #include "../../include/osgpu_reduce.h"
 #include "call_common.hpp"
 #include "combine.hpp"
+#include "loc_host.hpp"
 #include "many_host.hpp"
 #include "rscatter_host.hpp"
 #include "runtime.hpp"
@@ -1180,10 +1181,13 @@ void zero_ld_padding(const Call &c, void *p)
 // TEAM of the scan and the uniform reduce (`what`): every member launches the
 // kernel, launch(P, dsts, srcs, n, stream), over its own contiguous shard of
 // all P targets, between the two barriers.  (No tiles / merge scheme of local
-// members: run_team's bookkeeping is the reduce-to-all's.)
+// members: run_team's bookkeeping is the reduce-to-all's.)  cut_elem: the
+// element size shard_of cuts by when it is not the type's (osgpu_reduce_loc:
+// a second stream of 4-byte elements shares the boundaries).
 template <class Launch>
 void run_team_shards(const Call &c, const std::vector<const void *> &srcs,
-                     const std::vector<void *> &dsts, int idx, const char *what, Launch launch)
+                     const std::vector<void *> &dsts, int idx, const char *what, Launch launch,
+                     size_t cut_elem = 0)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const size_t s = type_size(c.type);
@@ -1192,7 +1196,7 @@ void run_team_shards(const Call &c, const std::vector<const void *> &srcs,
     entry_sync(c.name, st);
     barrier(c);  // every source is ready, every target writable
     long long lo = 0, hi = 0;
-    shard_of(c.nreduce, P, idx, s, &lo, &hi);
+    shard_of(c.nreduce, P, idx, cut_elem ? cut_elem : s, &lo, &hi);
     std::vector<const void *> sp(P);
     std::vector<void *> dp(P);
     for (int i = 0; i < P; i++) {
@@ -1470,6 +1474,287 @@ void reduce_uniform(const char *name, int type, int op, void *target, const void
         run_uniform_pull(c);
 }
 
+// ------------------------------------------- max / min with location
+//
+// osgpu_reduce_loc: the uniform reduce's one ascending fold over pairs
+// (value, 32-bit index): every member receives the extreme and where it came
+// from (elem_ops.hpp LocStep).  Paths: device heaps the owner-computes kernel
+// (launch_team_loc with every member's targets) or the pull form (the
+// caller's targets alone, in chunks of 8 inputs); host heaps the host fold
+// and GETMEM.  No FUSED, STAGED, RCCL or push form.  The byte arithmetic, the
+// overlap rule and the chunk walks are loc_host.hpp's.
+
+struct LocCall : Call {
+    int *loc_target = nullptr;
+    const int *loc_source = nullptr;  // null: member j's elements carry its PE number
+    size_t lbytes = 0;
+    int member_pe(int j) const { return pe_at(j); }
+};
+
+// `p`, nbytes long, in my registered heap: every member's copy of it
+bool symmetric_ptrs(const Coll &c, const void *p, size_t nbytes, std::vector<char *> &out)
+{
+    int seg = -1;
+    size_t off = 0;
+    if (!heap_locate(c.me, p, nbytes, &seg, &off)) return false;
+    out.resize(c.PE_size);
+    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step)
+        if (!heap_peer(pe, seg, off, nbytes, &out[i])) return false;
+    return true;
+}
+
+// TEAM: all four arrays (three without index sources) symmetric, nothing
+// overlapping, 2..8 members.  Every member folds its shard of all targets.
+// Shards are cut with element size min(sizeof(T), 4): every boundary is then
+// a multiple of the kernel's group for both streams (with 8 for an 8-byte
+// type the index stream would start 8 bytes off a vector on every shard but
+// the first).
+bool run_loc_team(const LocCall &c)
+{
+    const int P = c.PE_size;
+    if (P < 2 || P > osgpu::kMaxTeam) return false;
+    if (ranges_overlap(c.target, c.nbytes, c.source, c.nbytes) ||
+        (c.loc_source && ranges_overlap(c.loc_target, c.lbytes, c.loc_source, c.lbytes)))
+        return false;
+    std::vector<char *> vs, vd, ls, ld;
+    if (!symmetric_ptrs(c, c.source, c.nbytes, vs) || !symmetric_ptrs(c, c.target, c.nbytes, vd) ||
+        !symmetric_ptrs(c, c.loc_target, c.lbytes, ld) ||
+        (c.loc_source && !symmetric_ptrs(c, c.loc_source, c.lbytes, ls)))
+        return false;
+    const size_t s = type_size(c.type);
+    std::vector<const void *> srcs(vs.begin(), vs.end());
+    std::vector<void *> dsts(vd.begin(), vd.end());
+    std::vector<int> member(P);
+    for (int j = 0; j < P; j++) member[j] = c.member_pe(j);
+    run_team_shards(
+        c, srcs, dsts, c.index_of(c.me), "team max/min with location",
+        [&](int np, void *const *d, const void *const *sr, size_t n, hipStream_t st) {
+            const size_t lo = (size_t) ((const char *) sr[0] - (const char *) srcs[0]) / s;
+            std::vector<int *> lt(np);
+            std::vector<const int *> lsrc(np);
+            for (int j = 0; j < np; j++) {
+                lt[j] = (int *) ld[j] + lo;
+                if (c.loc_source) lsrc[j] = (const int *) ls[j] + lo;
+            }
+            return osgpu::launch_team_loc(c.type, c.op, np, np, d, lt.data(), sr,
+                                          c.loc_source ? lsrc.data() : nullptr, member.data(), n,
+                                          st);
+        },
+        s < 4 ? s : 4);
+    return true;
+}
+
+// PULL: the caller folds all P pairs itself, ascending, into its own targets:
+// launches of at most 8 inputs, the pair folded so far fed back as input 0.
+// A target that overlaps its source is folded into scratch and copied back
+// after the exit barrier.
+void run_loc_pull(const LocCall &c)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size;
+    std::vector<char *> vs, ls;
+    if (!symmetric_ptrs(c, c.source, c.nbytes, vs) ||
+        (c.loc_source && !symmetric_ptrs(c, c.loc_source, c.lbytes, ls)))
+        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
+                      "(osgpu_heap_create / osgpu_heap_register) and the %zu-byte source%s inside it",
+              c.nbytes, c.loc_source ? " and the index source" : "");
+    t_last_path = OSGPU_RAN_PULL;
+    DBG("%s PE %d: pull over %d members, ascending", c.name, c.me, P);
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready
+    const bool ov = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const bool ol = c.loc_source && ranges_overlap(c.loc_target, c.lbytes, c.loc_source, c.lbytes);
+    const size_t vslot = (c.nbytes + 15) & ~(size_t) 15;
+    char *scr = ov || ol ? (char *) device_scratch(c.name, c.me, vslot + c.lbytes) : nullptr;
+    void *vout = ov ? (void *) scr : c.target;
+    int *lout = ol ? (int *) (scr + vslot) : c.loc_target;
+    loc_for_input_chunks(P, [&](int first, int count, bool feedback) {
+        const void *v[kLocMaxInputs];
+        const int *l[kLocMaxInputs];
+        int member[kLocMaxInputs], k = 0;
+        if (feedback) v[k] = vout, l[k] = lout, member[k] = 0, k++;
+        for (int j = first; j < first + count; j++, k++) {
+            v[k] = vs[j];
+            l[k] = c.loc_source ? (const int *) ls[j] : nullptr;
+            member[k] = c.member_pe(j);
+        }
+        launched(c.name, "max/min with location launch",
+                 osgpu::launch_team_loc(c.type, c.op, k, 1, &vout, &lout, v,
+                                        c.loc_source || feedback ? l : nullptr, member,
+                                        (size_t) c.nreduce, st));
+    });
+    stream_wait(c.name, st);
+    barrier(c);  // peers are done reading my sources
+    if (ov) HIPCHK(c.name, hipMemcpyAsync(c.target, vout, c.nbytes, hipMemcpyDeviceToDevice, st));
+    if (ol) HIPCHK(c.name, hipMemcpyAsync(c.loc_target, lout, c.lbytes, hipMemcpyDeviceToDevice, st));
+    if (ov || ol) stream_wait(c.name, st);
+}
+
+// member j's bytes [off, off + nb) of the symmetric host array `mine` as this
+// member sees them: its own array, or one getmem into `buf`
+const void *loc_host_input(const LocCall &c, const void *mine, int j, size_t off, size_t nb,
+                           void *buf)
+{
+    const int pe = c.member_pe(j);
+    const char *src = (const char *) mine + off;
+    if (pe == c.me) return src;
+    c.ops.getmem(buf, src, nb, pe);
+    return buf;
+}
+
+// Host heaps, small calls: the fold on this PE's thread, ascending, one
+// getmem of each whole array per peer.
+void run_loc_host_fold(const LocCall &c)
+{
+    t_last_path = OSGPU_RAN_HOST_FOLD;
+    const int P = c.PE_size;
+    const size_t N = (size_t) c.nreduce;
+    const bool ov = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const bool ol = c.loc_source && ranges_overlap(c.loc_target, c.lbytes, c.loc_source, c.lbytes);
+    thread_local std::vector<unsigned char> tv, tl, pv, pl;
+    if (ov) tv.resize(c.nbytes);
+    if (ol) tl.resize(c.lbytes);
+    pv.resize(c.nbytes);
+    pl.resize(c.lbytes);
+    void *accv = ov ? (void *) tv.data() : c.target;
+    int *accl = ol ? (int *) tl.data() : c.loc_target;
+    barrier(c);  // every source is ready
+    memmove(accv, loc_host_input(c, c.source, 0, 0, c.nbytes, pv.data()), c.nbytes);
+    if (c.loc_source)
+        memmove(accl, loc_host_input(c, c.loc_source, 0, 0, c.lbytes, pl.data()), c.lbytes);
+    else
+        std::fill(accl, accl + N, c.member_pe(0));
+    for (int j = 1; j < P; j++) {
+        const void *bv = loc_host_input(c, c.source, j, 0, c.nbytes, pv.data());
+        const int *bl = c.loc_source
+                            ? (const int *) loc_host_input(c, c.loc_source, j, 0, c.lbytes, pl.data())
+                            : nullptr;
+        if (!osgpu::host_fold_loc(c.type, c.op, accv, accl, bv, bl, c.member_pe(j), N))
+            fatal(c.name, "host fold: type %d op %d", c.type, c.op);
+    }
+    barrier(c);  // every peer is done reading my sources
+    if (ov) memcpy(c.target, accv, c.nbytes);
+    if (ol) memcpy(c.loc_target, accl, c.lbytes);
+}
+
+// Host heaps above that: chunks of host_chunk_bytes() (loc_chunk_elems), BOTH
+// streams of a chunk pulled into pinned staging before it is folded on the
+// GPU, at most 8 inputs a launch.
+void run_loc_host(const LocCall &c)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size, K = std::min(P, (int) kLocMaxInputs);
+    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
+    t_last_path = OSGPU_RAN_GETMEM;
+    const bool ov = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    const bool ol = c.loc_source && ranges_overlap(c.loc_target, c.lbytes, c.loc_source, c.lbytes);
+    HostTmp resv(c, c.target, ov, c.nbytes), resl(c, c.loc_target, ol, c.lbytes);
+    barrier(c);  // every source is ready
+    // slots 0 .. K-1 the inputs, slot K the result; the value slots first
+    const size_t chunk = loc_chunk_elems(host_chunk_bytes(), s, N);
+    const size_t vb = chunk * s, lb = chunk * kLocIndexBytes, loff = (size_t) (K + 1) * vb;
+    const size_t total = loff + (size_t) (K + 1) * lb;
+    char *dbuf = (char *) device_scratch(c.name, c.me, total);
+    char *hbuf = (char *) host_stage(c.name, c.me, total);
+    void *dvout = dbuf + (size_t) K * vb;
+    int *dlout = (int *) (dbuf + loff + (size_t) K * lb);
+    scan_for_chunks(N, chunk, [&](size_t off, size_t n) {
+        const size_t nvb = n * s, nlb = n * kLocIndexBytes;
+        loc_for_input_chunks(P, [&](int first, int count, bool feedback) {
+            const void *v[kLocMaxInputs];
+            const int *l[kLocMaxInputs];
+            int member[kLocMaxInputs], k = 0;
+            if (feedback) v[k] = dvout, l[k] = dlout, member[k] = 0, k++;
+            for (int j = first, slot = 0; j < first + count; j++, k++, slot++) {
+                char *hv = hbuf + (size_t) slot * vb, *hl = hbuf + loff + (size_t) slot * lb;
+                char *dv = dbuf + (size_t) slot * vb, *dl = dbuf + loff + (size_t) slot * lb;
+                const void *in = loc_host_input(c, c.source, j, off * s, nvb, hv);
+                if (in != hv) memcpy(hv, in, nvb);
+                HIPCHK(c.name, hipMemcpyAsync(dv, hv, nvb, hipMemcpyHostToDevice, st));
+                if (c.loc_source) {
+                    in = loc_host_input(c, c.loc_source, j, off * kLocIndexBytes, nlb, hl);
+                    if (in != hl) memcpy(hl, in, nlb);
+                    HIPCHK(c.name, hipMemcpyAsync(dl, hl, nlb, hipMemcpyHostToDevice, st));
+                }
+                v[k] = dv;
+                l[k] = c.loc_source ? (const int *) dl : nullptr;
+                member[k] = c.member_pe(j);
+            }
+            launched(c.name, "max/min with location launch",
+                     osgpu::launch_team_loc(c.type, c.op, k, 1, &dvout, &dlout, v,
+                                            c.loc_source || feedback ? l : nullptr, member, n, st));
+            stream_wait(c.name, st);  // the staging slots are reused by the next launch
+        });
+        char *hvout = hbuf + (size_t) K * vb, *hlout = hbuf + loff + (size_t) K * lb;
+        HIPCHK(c.name, hipMemcpyAsync(hvout, dvout, nvb, hipMemcpyDeviceToHost, st));
+        HIPCHK(c.name, hipMemcpyAsync(hlout, dlout, nlb, hipMemcpyDeviceToHost, st));
+        stream_wait(c.name, st);
+        memcpy(resv.out + off * s, hvout, nvb);
+        memcpy(resl.out + off * kLocIndexBytes, hlout, nlb);
+    });
+    barrier(c);  // every peer is done reading my sources
+    resv.finish(c.nbytes);
+    resl.finish(c.lbytes);
+}
+
+void reduce_loc(const char *name, int type, int op, void *target, int *loc_target,
+                const void *source, const int *loc_source, int nreduce, int PE_start,
+                int logPE_stride, int PE_size, long *pSync)
+{
+    if (!loc_pair(type, op))
+        fatal(name, "type %d op %d is no max / min with location of this library "
+                    "(osgpu_has_reduce_loc)", type, op);
+    LocCall c;
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    c.target = target;
+    c.source = const_cast<void *>(source);
+    c.loc_target = loc_target;
+    c.loc_source = loc_source;
+    c.nreduce = nreduce;
+    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
+        t_last_path = OSGPU_RAN_BARRIER_ONLY;
+        sync_only(c);
+        return;
+    }
+    LocBytes b;
+    if (!loc_bytes(type_size(type), nreduce, PE_size, loc_source != nullptr, &b))
+        fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
+    c.nbytes = b.vbytes;
+    c.lbytes = b.lbytes;
+    if (!target || !source || !loc_target) fatal(name, "a null array");
+    if (const char *pair = loc_cross_overlap(target, source, b.vbytes, loc_target, loc_source,
+                                             b.lbytes))
+        fatal(name, "%s overlap: a value array and an index array must not share a byte", pair);
+
+    int dev = -1, d2 = -1;
+    const MemKind kind = mem_kind(target, &dev);
+    if (mem_kind(source, &d2) != kind || mem_kind(loc_target, &d2) != kind ||
+        (loc_source && mem_kind(loc_source, &d2) != kind))
+        fatal(name, "the arrays must all be device or all be host memory");
+    if (kind == MEM_HOST) {
+        const int hp = host_path();
+        require_host_heaps(c);
+        const size_t fold_lim = host_fold_max_bytes();  // 0: off
+        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
+            osgpu::host_fold_loc_supported(type, op)) {
+            run_loc_host_fold(c);
+            return;
+        }
+        if (hp == OSGPU_HOST_STAGED)
+            DBG("%s PE %d: no STAGED form of the max / min with location, taking GETMEM", name,
+                c.me);
+        run_loc_host(c);
+        return;
+    }
+    const DeviceGuard on_device(name, dev);
+    // the team kernel under every setting but OSGPU_PATH_PULL (RCCL never
+    // serves this call); an overlap, an array outside the heaps, one member
+    // and more than 8 take the pull form
+    if (path_mode() == OSGPU_PATH_PULL || !run_loc_team(c)) run_loc_pull(c);
+}
+
 }  // namespace
 
 extern "C" int osgpu_last_path(void) { return t_last_path; }
@@ -1649,4 +1934,23 @@ extern "C" void osgpu_reduce_uniform(int type, int op, void *target, const void 
 extern "C" int osgpu_has_reduce_uniform(int type, int op)
 {
     return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+}
+
+// ======================================================================
+// Part 1h: max / min with location (no reference counterpart)
+// ======================================================================
+
+extern "C" void osgpu_reduce_loc(int type, int op, void *target, int *loc_target,
+                                 const void *source, const int *loc_source, int nreduce,
+                                 int PE_start, int logPE_stride, int PE_size, void *pWrk,
+                                 long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    reduce_loc("osgpu_reduce_loc", type, op, target, loc_target, source, loc_source, nreduce,
+               PE_start, logPE_stride, PE_size, pSync);
+}
+
+extern "C" int osgpu_has_reduce_loc(int type, int op)
+{
+    return osgpu::rt::loc_pair(type, op) ? 1 : 0;
 }

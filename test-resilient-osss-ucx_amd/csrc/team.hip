@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "kernel_common.hpp"
+#include "loc_host.hpp"
 #include "scan_host.hpp"
 
 #pragma clang fp contract(off)
@@ -943,6 +944,231 @@ hipError_t launch_team_uniform(int type, int op, int P, void *const *dsts, const
         if (n == 0) return hipSuccess;
         return uniform_launch_op<typename decltype(t)::type, decltype(o)::value>(P, dsts, srcs, n,
                                                                                  s);
+    });
+}
+
+// ------------------------------------------- max / min with location
+// osgpu_reduce_loc: the uniform reduce's ONE ascending fold carrying a second
+// stream -- every element is a pair (value, 32-bit index), folded by
+// elem_ops.hpp LocStep, and both results go to ndst targets (all P members'
+// in the owner-computes form, the caller's alone in the pull form).  The
+// kernel reads P value streams and up to P index streams whose elements
+// differ in size, so a lane step is a GROUP of G = max(16 / sizeof(T), 4)
+// elements: whole 16-byte vectors of both streams (loc_host.hpp loc_group).
+//
+// Register form, no LDS and no barrier: the fold of a group needs nothing
+// from another lane, and the LDS tile of team_uniform_lds_kernel costs it
+// 3-16 % on HBM-bound types.  A lane issues the
+// P * (NV + NI) loads of its group -- 24 at 8 members -- before the first
+// use, folds G elements (a compare pair and two selects per member), and
+// stores ndst * (NV + NI) vectors.  One group per lane and ONE bounds test
+// around the whole body: a lane beyond the last group leaves, so no load is
+// conditional and nothing merges at a join (the uniform kernel's clamped
+// index is not needed: at most 76 VGPRs at 8 members, 6 waves per SIMD or
+// more, no scratch).
+// Index sources are a template parameter: kLocConst reads no index stream at
+// all (every element of member p carries a.member[p]); kLocFeedback reads
+// input 0's only (the pull form's chunks after the first, whose input 0 is
+// the pair folded so far).
+constexpr int kLocBlock = 256;  // groups per tile: one per lane
+enum LocMode { kLocConst = 0, kLocStreams = 1, kLocFeedback = 2 };
+
+template <typename T, int P>
+struct LocPtrs {
+    const T *vsrc[P];
+    const int32_t *lsrc[P];
+    T *vdst[P];
+    int32_t *ldst[P];
+    int32_t member[P];
+};
+
+template <int MODE>
+__device__ __forceinline__ constexpr bool loc_streamed(int p)
+{
+    return MODE == kLocStreams || (MODE == kLocFeedback && p == 0);
+}
+
+template <typename T, int OP, int P, int MODE>
+__global__ __launch_bounds__(kLocBlock) void team_loc_vec_kernel(LocPtrs<T, P> a, int ndst,
+                                                                 size_t ngroups, size_t head,
+                                                                 size_t tail_start, int nedge)
+{
+    constexpr int G = sizeof(T) == 2 ? 8 : 4;  // elements per group
+    constexpr int W = 16 / sizeof(T);          // values per vector
+    constexpr int NV = G / W, NI = G / 4;      // vectors per group and stream
+    if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
+        const size_t e = edge_index(head, tail_start);
+        T v = a.vsrc[0][e];
+        int32_t i = loc_streamed<MODE>(0) ? a.lsrc[0][e] : a.member[0];
+#pragma unroll
+        for (int p = 1; p < P; p++)
+            LocStep<T, OP>::f(v, i, a.vsrc[p][e], loc_streamed<MODE>(p) ? a.lsrc[p][e] : a.member[p]);
+#pragma unroll
+        for (int q = 0; q < P; q++)
+            if (q < ndst) {
+                a.vdst[q][e] = v;
+                a.ldst[q][e] = i;
+            }
+    }
+    const size_t j = (size_t) blockIdx.x * kLocBlock + threadIdx.x;
+    if (j >= ngroups) return;
+    Vec16<T> val[P][NV];
+    Vec16<int32_t> loc[P][NI];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+#pragma unroll
+        for (int u = 0; u < NV; u++)
+            val[p][u].v = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4 *>(a.vsrc[p] + head) + j * NV + u);
+        if (loc_streamed<MODE>(p)) {
+#pragma unroll
+            for (int u = 0; u < NI; u++)
+                loc[p][u].v = __builtin_nontemporal_load(
+                    reinterpret_cast<const u32x4 *>(a.lsrc[p] + head) + j * NI + u);
+        }
+    }
+    Vec16<T> rv[NV];
+    Vec16<int32_t> ri[NI];
+#pragma unroll
+    for (int e = 0; e < G; e++) {
+        T v = val[0][e / W].e[e % W];
+        int32_t i = loc_streamed<MODE>(0) ? loc[0][e / 4].e[e % 4] : a.member[0];
+#pragma unroll
+        for (int p = 1; p < P; p++)
+            LocStep<T, OP>::f(v, i, val[p][e / W].e[e % W],
+                              loc_streamed<MODE>(p) ? loc[p][e / 4].e[e % 4] : a.member[p]);
+        rv[e / W].e[e % W] = v;
+        ri[e / 4].e[e % 4] = i;
+    }
+#pragma unroll
+    for (int q = 0; q < P; q++) {
+        if (q >= ndst) break;
+#pragma unroll
+        for (int u = 0; u < NV; u++)
+            __builtin_nontemporal_store(rv[u].v,
+                                        reinterpret_cast<u32x4 *>(a.vdst[q] + head) + j * NV + u);
+#pragma unroll
+        for (int u = 0; u < NI; u++)
+            __builtin_nontemporal_store(ri[u].v,
+                                        reinterpret_cast<u32x4 *>(a.ldst[q] + head) + j * NI + u);
+    }
+}
+
+// element-granular form (no common head aligns every pointer): np members of
+// a table sized for kMaxTeam, so one instantiation per mode serves every P
+template <typename T, int OP, int MODE>
+__global__ __launch_bounds__(kTeamBlock) void team_loc_scalar_kernel(LocPtrs<T, kMaxTeam> a, int np,
+                                                                     int ndst, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * kTeamBlock;
+    for (size_t k = (size_t) blockIdx.x * kTeamBlock + threadIdx.x; k < n; k += stride) {
+        T v = a.vsrc[0][k];
+        int32_t i = loc_streamed<MODE>(0) ? a.lsrc[0][k] : a.member[0];
+#pragma unroll
+        for (int p = 1; p < kMaxTeam; p++)
+            if (p < np)
+                LocStep<T, OP>::f(v, i, a.vsrc[p][k],
+                                  loc_streamed<MODE>(p) ? a.lsrc[p][k] : a.member[p]);
+#pragma unroll
+        for (int q = 0; q < kMaxTeam; q++)
+            if (q < ndst) {
+                a.vdst[q][k] = v;
+                a.ldst[q][k] = i;
+            }
+    }
+}
+
+template <typename T, int P>
+static LocPtrs<T, P> loc_ptrs(int np, int ndst, void *const *vd, int *const *ld,
+                              const void *const *vs, const int *const *ls, const int *member,
+                              int mode, size_t off)
+{
+    LocPtrs<T, P> a;
+    for (int p = 0; p < P; p++) {
+        const bool streamed = mode == kLocStreams || (mode == kLocFeedback && p == 0);
+        a.vsrc[p] = p < np ? static_cast<const T *>(vs[p]) + off : nullptr;
+        a.lsrc[p] = p < np && streamed ? ls[p] + off : nullptr;
+        a.vdst[p] = p < ndst ? static_cast<T *>(vd[p]) + off : nullptr;
+        a.ldst[p] = p < ndst ? ld[p] + off : nullptr;
+        a.member[p] = p < np && !streamed ? member[p] : 0;
+    }
+    return a;
+}
+
+template <typename T, int OP, int MODE>
+static hipError_t loc_launch_mode(int P, int ndst, void *const *vd, int *const *ld,
+                                  const void *const *vs, const int *const *ls, const int *member,
+                                  size_t n, hipStream_t s)
+{
+    const void *vals[2 * kMaxTeam], *locs[2 * kMaxTeam];
+    int nv = 0, nl = 0;
+    for (int p = 0; p < P; p++) vals[nv++] = vs[p];
+    for (int q = 0; q < ndst; q++) vals[nv++] = vd[q], locs[nl++] = ld[q];
+    for (int p = 0; p < P; p++)
+        if (MODE == kLocStreams || (MODE == kLocFeedback && p == 0)) locs[nl++] = ls[p];
+    const rt::LocSplit sp = rt::loc_split(sizeof(T), n, vals, nv, locs, nl);
+    if (!sp.vec) {
+        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
+        blocks = blocks > 8192 ? 8192 : blocks;
+        hipLaunchKernelGGL((team_loc_scalar_kernel<T, OP, MODE>), dim3((unsigned) blocks),
+                           dim3(kTeamBlock), 0, s,
+                           loc_ptrs<T, kMaxTeam>(P, ndst, vd, ld, vs, ls, member, MODE, 0), P, ndst,
+                           n);
+        return hipGetLastError();
+    }
+    constexpr size_t G = sizeof(T) == 2 ? 8 : 4;
+    auto run = [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        // one tile of kLocBlock groups per workgroup, in runs below the launch
+        // limit: the first launch takes the edges, the others shifted pointers
+        return for_each_tile_run(sp.ngroups, kLocBlock, kLocBlock, 1,
+                                 [&](size_t t0, size_t nt, size_t ng) {
+            const size_t off = t0 == 0 ? 0 : sp.head + t0 * kLocBlock * G;
+            hipLaunchKernelGGL((team_loc_vec_kernel<T, OP, PP, MODE>), dim3((unsigned) nt),
+                               dim3(kLocBlock), 0, s,
+                               loc_ptrs<T, PP>(PP, ndst, vd, ld, vs, ls, member, MODE, off), ndst,
+                               ng, t0 == 0 ? sp.head : (size_t) 0,
+                               t0 == 0 ? sp.tail_start : (size_t) 0, t0 == 0 ? sp.nedge : 0);
+            return hipGetLastError();
+        });
+    };
+    if (P == 1) return run(std::integral_constant<int, 1>{});
+    return dispatch_members(P, hipErrorInvalidValue, run);
+}
+
+hipError_t launch_team_loc(int type, int op, int P, int ndst, void *const *val_dsts,
+                           int *const *loc_dsts, const void *const *val_srcs,
+                           const int *const *loc_srcs, const int *member_locs, size_t n,
+                           hipStream_t s)
+{
+    if (P < 1 || P > kMaxTeam || (ndst != 1 && ndst != P)) return hipErrorInvalidValue;
+    if (op != OP_MAX && op != OP_MIN) return hipErrorInvalidValue;
+    if (!val_dsts || !loc_dsts || !val_srcs || (!loc_srcs && !member_locs))
+        return hipErrorInvalidValue;
+    int mode = kLocConst;
+    if (loc_srcs && loc_srcs[0]) mode = P == 1 || loc_srcs[1] ? kLocStreams : kLocFeedback;
+    if (mode == kLocFeedback && !member_locs) return hipErrorInvalidValue;
+    return dispatch_type_op(type, op, hipErrorInvalidValue, [&](auto t, auto o) {
+        using T = typename decltype(t)::type;
+        constexpr int OP = decltype(o)::value;
+        constexpr bool kOrdered = std::is_integral<T>::value || std::is_floating_point<T>::value ||
+                                  is_f16<T>::value;
+        if constexpr (kOrdered && (OP == OP_MAX || OP == OP_MIN)) {
+            if (n == 0) return hipSuccess;
+            switch (mode) {
+            case kLocConst:
+                return loc_launch_mode<T, OP, kLocConst>(P, ndst, val_dsts, loc_dsts, val_srcs,
+                                                         loc_srcs, member_locs, n, s);
+            case kLocStreams:
+                return loc_launch_mode<T, OP, kLocStreams>(P, ndst, val_dsts, loc_dsts, val_srcs,
+                                                           loc_srcs, member_locs, n, s);
+            default:
+                return loc_launch_mode<T, OP, kLocFeedback>(P, ndst, val_dsts, loc_dsts, val_srcs,
+                                                            loc_srcs, member_locs, n, s);
+            }
+        } else {
+            return hipErrorInvalidValue;
+        }
     });
 }
 

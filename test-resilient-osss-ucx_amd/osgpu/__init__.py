@@ -170,6 +170,10 @@ def load() -> ctypes.CDLL:
     L.osgpu_reduce_uniform.restype = None
     L.osgpu_has_reduce_uniform.argtypes = [i, i]
     L.osgpu_team_uniform.argtypes = [i, i, i, vp, vp, sz, vp]
+    L.osgpu_reduce_loc.argtypes = [i, i, vp, vp, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_reduce_loc.restype = None
+    L.osgpu_has_reduce_loc.argtypes = [i, i]
+    L.osgpu_team_loc.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -479,6 +483,34 @@ def team_uniform(t: str, op: str, dsts, srcs, n: int, stream: int | None = None,
                               (ctypes.c_void_p * P)(*srcs), n, stream)
     if rc != 0 and check:
         raise RuntimeError(f"osgpu_team_uniform({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
+
+
+def reduce_loc(t: str, op: str):
+    """osgpu_reduce_loc bound to the codes of (t, op), op "max" or "min": a
+    function of (target, loc_target, source, loc_source, nreduce, PE_start,
+    logPE_stride, PE_size, pWrk, pSync); every member receives the extreme and
+    its index by one ascending fold.  loc_source None: the members' PE numbers."""
+    f, tc, oc = load().osgpu_reduce_loc, type_code(t), OPS.index(op)
+    return lambda *args: f(tc, oc, *args)
+
+
+def team_loc(t: str, op: str, val_dsts, loc_dsts, val_srcs, loc_srcs, n: int, member_locs=None,
+             stream: int | None = None, check: bool = True) -> int:
+    """Enqueue the value + index kernel: every (val_dsts[q], loc_dsts[q]) = the
+    ascending fold of the pairs (val_srcs[p], loc_srcs[p]) (device ptrs);
+    len(val_dsts) is 1 or len(val_srcs).  loc_srcs None: input p's elements all
+    carry member_locs[p].  Returns the status; check=True raises on a non-zero
+    one."""
+    L = load()
+    P, D = len(val_srcs), len(val_dsts)
+    ls = (ctypes.c_void_p * P)(*loc_srcs) if loc_srcs is not None else None
+    ml = (ctypes.c_int * P)(*member_locs) if member_locs is not None else None
+    rc = L.osgpu_team_loc(type_code(t), OPS.index(op), P, D, (ctypes.c_void_p * D)(*val_dsts),
+                          (ctypes.c_void_p * D)(*loc_dsts), (ctypes.c_void_p * P)(*val_srcs), ls,
+                          ml, n, stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_team_loc({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
     return rc
 
 
