@@ -1,10 +1,9 @@
 // rscatter_host.hpp -- the HIP-free arithmetic of osgpu_reduce_scatter's host
 // paths (shmem_reduce.cpp): which bytes of the P * nreduce element source a
-// member folds, and the host fold's loop over them.  No HIP, no runtime: also
-// built into tests/support/rscatter_host_check with ASan + UBSan.
+// member folds.  No HIP, no runtime: also built into
+// tests/support/rscatter_host_check with ASan + UBSan.
 #pragma once
 #include <stddef.h>
-#include <string.h>
 
 namespace osgpu {
 namespace rt {
@@ -32,34 +31,9 @@ inline bool rs_block(size_t elem, long long nreduce, int P, int m, RsBlock *b)
     return true;
 }
 
-// GETMEM's chunk in elements: chunk_bytes' worth, at least one, at most the
-// block, rounded up to an even count (as run_host does)
-inline size_t rs_chunk_elems(size_t chunk_bytes, size_t elem, size_t nreduce)
-{
-    size_t c = chunk_bytes / elem;
-    if (c == 0) c = 1;
-    if (c > nreduce) c = nreduce;
-    return (c + 1) & ~(size_t) 1;
-}
-
-// The host fold of one member: acc = my own block, then every other member's
-// block in my fold order (order[0] is me), each pulled by ONE getmem of
-// exactly b.bytes from source + b.offset into `peer` (b.bytes, unused when
-// P == 1: pass nullptr).  between(): called once after the own copy (the
-// entry barrier).  false when a fold step fails.
-template <class Getmem, class Fold, class Between>
-bool rs_host_fold(const RsBlock &b, const void *source, void *acc, void *peer, const int *order,
-                  int P, size_t nreduce, Getmem getmem, Fold fold, Between between)
-{
-    const char *mine = (const char *) source + b.offset;
-    if (b.bytes) memmove(acc, mine, b.bytes);
-    between();
-    for (int k = 1; k < P; k++) {
-        getmem(peer, mine, b.bytes, order[k]);
-        if (!fold(acc, peer, nreduce)) return false;
-    }
-    return true;
-}
+// GETMEM's chunk is every collective's (scan_host.hpp host_chunk_elems) over
+// the block; the host fold is the batched call's over a table of one entry
+// whose source is block m, source + offset (many_host.hpp many_host_fold).
 
 }  // namespace rt
 }  // namespace osgpu

@@ -1,8 +1,8 @@
 // scan_host.hpp -- the HIP-free arithmetic of osgpu_scan (shmem_reduce.cpp,
 // team.hip): how many members' sources a member folds, the bytes it pulls on
-// the host paths, GETMEM's chunk walk, and the identity of every (type, op)
-// as element bytes.  No HIP, no runtime: also built into
-// tests/support/scan_host_check with ASan + UBSan.
+// the host paths, the chunk and the chunk walk of every collective's GETMEM
+// form, and the identity of every (type, op) as element bytes.  No HIP, no
+// runtime: also built into tests/support/scan_host_check with ASan + UBSan.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -43,9 +43,10 @@ inline bool scan_bytes(size_t elem, long long nreduce, int P, int m, int exclusi
     return true;
 }
 
-// GETMEM's chunk in elements: chunk_bytes' worth, at least one, at most the
-// array, rounded up to an even count (as run_host does)
-inline size_t scan_chunk_elems(size_t chunk_bytes, size_t elem, size_t nreduce)
+// The chunk of every GETMEM form (shmem_reduce.cpp getmem_chunks) in
+// elements: chunk_bytes' worth, at least one, at most the array (the
+// reduce-scatter's block), rounded up to an even count
+inline size_t host_chunk_elems(size_t chunk_bytes, size_t elem, size_t nreduce)
 {
     size_t c = chunk_bytes / elem;
     if (c == 0) c = 1;

@@ -24,6 +24,14 @@
 // The two shmem_barrier calls of the reference (:82, :113) keep their roles
 // (every source ready / every reader or writer done) on every non-RCCL path.
 // The per-call scaffolding shared with shmem_collect.cpp is call_common.hpp.
+//
+// The other front doors (reduce-scatter, batched, scan, uniform, max/min with
+// location) have no forms of their own above the kernels: they share the
+// reduce-to-all's prologue (begin_call, arrays_kind), its host route
+// (host_route_fold), its GETMEM chunk loop (getmem_chunks), its pull schedule
+// (symmetric_ptrs, fold_sources, run_pull) and its caller-first host fold
+// (host_fold_table), and pass what differs -- the members to read, a byte
+// offset, the launcher, an overlap verdict -- as arguments.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
@@ -62,19 +70,103 @@ struct Call : Coll {
     size_t nbytes = 0;
 };
 
-// every member's source in active-set order (both pull forms)
-bool member_sources(const Call &c, std::vector<const void *> &srcs)
+// ----------------------------------------------------------- the prologue
+
+// What every front door starts with: the active set (make_coll's checks) and
+// the arrays.  `empty`: nothing to combine -- the collective still syncs, and
+// the door returns.  false then.
+bool begin_call(Call &c, const char *name, int type, int op, void *target, const void *source,
+                int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync, bool empty)
+{
+    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
+    c.type = type;
+    c.op = op;
+    c.target = target;
+    c.source = const_cast<void *>(source);
+    c.nreduce = nreduce;
+    if (!empty) return true;
+    t_last_path = OSGPU_RAN_BARRIER_ONLY;
+    sync_only(c);
+    return false;
+}
+
+bool is_reduction(int type, int op) { return has_op(type, op) || has_ext_op(type, op); }
+
+// `has`: the osgpu_has_* query that answers for the call
+void require_reduction(const char *name, int type, int op, const char *has)
+{
+    if (!is_reduction(type, op))
+        fatal(name, "type %d op %d is not a reduction of this library (%s)", type, op, has);
+}
+
+// The arrays of a call are all device or all host memory: the kind, and the
+// first array's device.  heap_first (the batched call's long tables): an
+// array after the first inside my registered device heap needs no pointer
+// query.
+struct Array {
+    const void *p;
+    size_t bytes;
+};
+MemKind arrays_kind(const Coll &c, const Array *arrays, size_t count, int *dev,
+                    bool heap_first = false)
+{
+    const MemKind kind = mem_kind(arrays[0].p, dev);
+    for (size_t i = 1; i < count; i++) {
+        int seg = -1, d = -1;
+        size_t off = 0;
+        const bool in_heap =
+            heap_first && heap_locate(c.me, arrays[i].p, arrays[i].bytes, &seg, &off);
+        if ((in_heap ? MEM_DEVICE : mem_kind(arrays[i].p, &d)) != kind)
+            fatal(c.name, "the arrays must all be device or all be host memory");
+    }
+    return kind;
+}
+
+// Host heaps: the host fold (true), or the forms that cross the GPU.  The
+// fold serves small calls under OSGPU_HOST_AUTO (hp: host_path()):
+// `pulled_bound` is a size every member shares, so all of them take the same
+// path.  `no_staged`: what to call a collective without a STAGED form in the
+// trace (null: it has one).
+bool host_route_fold(const Call &c, int hp, size_t pulled_bound, bool fold_supported,
+                     const char *no_staged)
+{
+    require_host_heaps(c);
+    const size_t fold_lim = host_fold_max_bytes();  // 0: off
+    if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && pulled_bound <= fold_lim && fold_supported)
+        return true;
+    if (no_staged && hp == OSGPU_HOST_STAGED)
+        DBG("%s PE %d: no STAGED form of %s, taking GETMEM", c.name, c.me, no_staged);
+    return false;
+}
+
+// --------------------------------------------------- symmetric pointers
+
+// [p, p + nbytes) in my registered heap: every member's copy of it, in
+// active-set order.  *remote: one of them is another GPU's memory.
+template <class Ptr>  // char *, void *, const void *: what the launcher at hand takes
+bool symmetric_ptrs(const Coll &c, const void *p, size_t nbytes, std::vector<Ptr> &out,
+                    bool *remote = nullptr)
 {
     int seg = -1;
     size_t off = 0;
-    if (!heap_locate(c.me, c.source, c.nbytes, &seg, &off)) return false;
-    srcs.resize(c.PE_size);
-    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step) {
-        char *p = nullptr;
-        if (!heap_peer(pe, seg, off, c.nbytes, &p)) return false;
-        srcs[i] = p;
+    if (!heap_locate(c.me, p, nbytes, &seg, &off)) return false;
+    out.resize(c.PE_size);
+    for (int i = 0; i < c.PE_size; i++) {
+        char *q = nullptr;
+        bool far = false;
+        if (!heap_peer(c.pe_at(i), seg, off, nbytes, &q, &far)) return false;
+        out[i] = q;
+        if (remote && far) *remote = true;
     }
     return true;
+}
+
+// the one wording of the pull forms that have no other path
+[[noreturn]] void no_device_heap(const Coll &c, const char *what, size_t nbytes)
+{
+    fatal(c.name, "device-resident arguments need every active PE's device heap registered "
+                  "(osgpu_heap_create / osgpu_heap_register) and the whole %zu-byte %s inside it",
+          nbytes, what);
 }
 
 // Owner-computes team path (team.hip): needs both source and target inside
@@ -86,26 +178,12 @@ int team_ptrs(const Call &c, std::vector<const void *> &srcs, std::vector<void *
 {
     if (c.PE_size < 2 || c.PE_size > osgpu::kMaxTeam) return -1;
     if (ranges_overlap(c.target, c.nbytes, c.source, c.nbytes)) return -1;
-    int ss = -1, st = -1;
-    size_t os = 0, ot = 0;
-    if (!heap_locate(c.me, c.source, c.nbytes, &ss, &os)) return -1;
-    if (!heap_locate(c.me, c.target, c.nbytes, &st, &ot)) return -1;
-    srcs.resize(c.PE_size);
-    dsts.resize(c.PE_size);
-    int idx = -1;
     bool far = false;
-    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step) {
-        char *sp = nullptr, *tp = nullptr;
-        bool rs = false, rt_ = false;
-        if (!heap_peer(pe, ss, os, c.nbytes, &sp, &rs) || !heap_peer(pe, st, ot, c.nbytes, &tp, &rt_))
-            return -1;
-        srcs[i] = sp;
-        dsts[i] = tp;
-        far = far || rs || rt_;
-        if (pe == c.me) idx = i;
-    }
+    if (!symmetric_ptrs(c, c.source, c.nbytes, srcs, &far) ||
+        !symmetric_ptrs(c, c.target, c.nbytes, dsts, &far))
+        return -1;
     if (remote) *remote = far;
-    return idx;
+    return c.index_of(c.me);
 }
 
 // Members of one active set that are threads of THIS process on the same
@@ -288,26 +366,64 @@ void run_team_push(const Call &c, const std::vector<const void *> &srcs,
     }
 }
 
-// members: every member's source in active-set order (member_sources)
-void run_p2p(const Call &c, const std::vector<const void *> &members)
+// The members this PE folds, caller first (osgpu_fold_order), as PE numbers
+std::vector<int> caller_first(const Coll &c)
 {
-    hipStream_t st = pe_stream(c.name, c.me);
     std::vector<int> order(c.PE_size);
     fold_order(c.me, c.PE_start, c.step, c.PE_size, order.data());
-    std::vector<const void *> srcs(c.PE_size);  // in this PE's fold order
-    for (int k = 0; k < c.PE_size; k++) srcs[k] = members[c.index_of(order[k])];
+    return order;
+}
+
+// the first K members of the set, ascending (the scan, the uniform reduce)
+std::vector<int> ascending(const Coll &c, int K)
+{
+    std::vector<int> pes(K);
+    for (int k = 0; k < K; k++) pes[k] = c.pe_at(k);
+    return pes;
+}
+
+// `pes`' copies of the symmetric [p, p + nbytes), `off` bytes in, in the order
+// of `pes`.  false: not inside every member's registered heap.
+bool fold_sources(const Coll &c, const std::vector<int> &pes, const void *p, size_t nbytes,
+                  size_t off, const void **srcs)
+{
+    std::vector<char *> all;
+    if (!symmetric_ptrs(c, p, nbytes, all)) return false;
+    for (size_t k = 0; k < pes.size(); k++) srcs[k] = all[c.index_of(pes[k])] + off;
+    return true;
+}
+
+// PULL into my own target: the reference's schedule (src/reductions.c:82,
+// :113) around ONE launch over the sources the caller put in fold order.
+// `overlap`: peers read what the target overlaps, so the result goes to
+// scratch until they are done.  launch(out, stream) reports its own failure.
+template <class Launch>
+void run_pull(const Call &c, size_t out_bytes, bool overlap, Launch launch)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
     t_last_path = OSGPU_RAN_PULL;
     // prior device work of this process that produced `source` must be done
     entry_sync(c.name, st);
-    barrier(c);  // src/reductions.c:82 -- every source is ready
-    const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
-    const DeviceOut out(c, c.target, overlap, c.nbytes);
-    launched(c.name, "combine launch",
-             osgpu::launch_combine(c.type, c.op, out.out, srcs.data(), c.PE_size,
-                                   (size_t) c.nreduce, st));
+    barrier(c);  // :82 -- every source is ready
+    const DeviceOut out(c, c.target, overlap, out_bytes);
+    launch(out.out, st);
     stream_wait(c.name, st);
-    barrier(c);  // src/reductions.c:113 -- peers are done reading my source
-    out.finish(c.nbytes, st);
+    barrier(c);  // :113 -- peers are done reading my source
+    out.finish(out_bytes, st);
+}
+
+// members: every member's source in active-set order (symmetric_ptrs)
+void run_p2p(const Call &c, const std::vector<const void *> &members)
+{
+    const std::vector<int> order = caller_first(c);
+    std::vector<const void *> srcs(c.PE_size);  // in this PE's fold order
+    for (int k = 0; k < c.PE_size; k++) srcs[k] = members[c.index_of(order[k])];
+    const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
+    run_pull(c, c.nbytes, overlap, [&](void *out, hipStream_t st) {
+        launched(c.name, "combine launch",
+                 osgpu::launch_combine(c.type, c.op, out, srcs.data(), c.PE_size,
+                                       (size_t) c.nreduce, st));
+    });
 }
 
 // ---------------------------------------------------- fused small calls
@@ -598,45 +714,42 @@ void run_staged(const Call &c, StageSet &S)
 // memory (the UCX heap).  Peers' sources are pulled with the runtime's
 // shmem_getmem (src/putget.h:539-561), like the reference, but in large
 // chunks into pinned staging, then combined on the GPU.
-// The chunk loop between the two barriers: c's fold into `result` (the
-// target or its temporary).  Also run once per entry by run_many_host.
-void host_chunks(const Call &c, char *result)
+// The chunk loop between the two barriers of every GETMEM form: the fold of
+// c.nreduce elements from `off` bytes into c.source, read on the members
+// `pes` in that order, into `result` (the target or its temporary).  Per
+// chunk of host_chunk_bytes(): every input into its pinned slot (getmem, or
+// memcpy of my own), H2D, one launch of `launch` (launch_combine, or
+// launch_combine_shifted where the slots' 16-byte phases may differ from the
+// caller's arrays'), D2H, wait, memcpy to the result.
+void getmem_chunks(const Call &c, const std::vector<int> &pes, size_t off,
+                   decltype(&osgpu::launch_combine) launch, char *result)
 {
     hipStream_t st = pe_stream(c.name, c.me);
-    const size_t s = type_size(c.type);
-    const int P = c.PE_size;
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
+    const int K = (int) pes.size();
+    const size_t chunk = host_chunk_elems(host_chunk_bytes(), s, N), cb = chunk * s;
+    // device: K input slots + 1 output slot; pinned: K input slots + output
+    // (a slot of cb bytes need not be a multiple of 16)
+    char *dbuf = (char *) device_scratch(c.name, c.me, cb * (K + 1));
+    char *hbuf = (char *) host_stage(c.name, c.me, cb * (K + 1));
+    std::vector<const void *> srcs(K);
+    for (int k = 0; k < K; k++) srcs[k] = dbuf + (size_t) k * cb;
+    char *dout = dbuf + (size_t) K * cb, *hout = hbuf + (size_t) K * cb;
+    const char *mine = (const char *) c.source + off;
 
-    size_t chunk = host_chunk_bytes() / s;
-    if (chunk == 0) chunk = 1;
-    if (chunk > (size_t) c.nreduce) chunk = (size_t) c.nreduce;
-    chunk = (chunk + 1) & ~(size_t) 1;
-    const size_t cb = chunk * s;
-    // device: P input slots + 1 output slot; pinned: P input slots + output
-    char *dbuf = (char *) device_scratch(c.name, c.me, cb * (P + 1));
-    char *hbuf = (char *) host_stage(c.name, c.me, cb * (P + 1));
-    std::vector<const void *> srcs(P);
-    for (int k = 0; k < P; k++) srcs[k] = dbuf + (size_t) k * cb;
-
-    for (size_t off = 0; off < (size_t) c.nreduce; off += chunk) {
-        const size_t n = ((size_t) c.nreduce - off) < chunk ? ((size_t) c.nreduce - off) : chunk;
+    scan_for_chunks(N, chunk, [&](size_t at, size_t n) {
         const size_t nb = n * s;
-        for (int k = 0; k < P; k++) {
+        for (int k = 0; k < K; k++) {
             char *hk = hbuf + (size_t) k * cb;
-            const char *src = (const char *) c.source + off * s;
-            if (order[k] == c.me) memcpy(hk, src, nb);
-            else c.ops.getmem(hk, src, nb, order[k]);
+            if (pes[k] == c.me) memcpy(hk, mine + at * s, nb);
+            else c.ops.getmem(hk, mine + at * s, nb, pes[k]);
             HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
         }
-        char *dout = dbuf + (size_t) P * cb;
-        launched(c.name, "combine launch",
-                 osgpu::launch_combine(c.type, c.op, dout, srcs.data(), P, n, st));
-        char *hout = hbuf + (size_t) P * cb;
+        launched(c.name, "combine launch", launch(c.type, c.op, dout, srcs.data(), K, n, st));
         HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
         stream_wait(c.name, st);
-        memcpy(result + off * s, hout, nb);
-    }
+        memcpy(result + at * s, hout, nb);
+    });
 }
 
 void run_host(const Call &c)
@@ -645,14 +758,22 @@ void run_host(const Call &c)
     const bool overlap = c.PE_size > 1 && ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
     HostTmp result(c, c.target, overlap, c.nbytes);
     barrier(c);  // src/reductions.c:82
-    host_chunks(c, result.out);
+    getmem_chunks(c, caller_first(c), 0, osgpu::launch_combine, result.out);
     barrier(c);  // src/reductions.c:113
     result.finish(c.nbytes);  // src/reductions.c:114-119
 }
 
-// Small calls on HOST symmetric-heap memory (each PE pulling at most
-// host_fold_max_bytes() from its peers, automatic host path): the reference's algorithm on this PE's
-// thread with the kernels' element ops compiled for the host (host_fold.hip)
+// long double: bytes 10..15 of each of the n slots a COPY wrote at p are zero,
+// as after a fold
+void zero_ld_padding(int type, void *p, size_t n)
+{
+    if (type != osgpu::T_LONGDOUBLE) return;
+    for (size_t i = 0; i < n; i++) memset((char *) p + 16 * i + 10, 0, 6);
+}
+
+// Small calls on HOST symmetric-heap memory (each PE pulling at most the host
+// fold's limit from its peers, automatic host path): the reference's
+// algorithm on this PE's thread with the kernels' element ops compiled for the host (host_fold.hip)
 // -- the source copied into the target, barrier (src/reductions.c:82), every
 // other PE's whole source pulled with ONE shmem_getmem (the reference pulls
 // 64 elements per getmem, :90-103) and folded in this PE's order (:84-111),
@@ -660,31 +781,44 @@ void run_host(const Call &c)
 // No GPU round trip: below this size the fastest GPU form (one fused launch
 // reading and writing the host heap over PCIe) costs more than the whole
 // loop.
-void run_host_fold(const Call &c)
+// The table form, for every caller-first collective: accs[i] takes my own
+// sources[i] BEFORE the entry barrier, then every peer's in my fold order.
+// An accumulator is the entry's target, or the caller's temporary where the
+// target overlaps what peers still read; the caller copies it back.
+void host_fold_table(const Call &c, int M, void *const *accs, const void *const *sources,
+                     const size_t *bytes, const size_t *nelems)
 {
     t_last_path = OSGPU_RAN_HOST_FOLD;
     const int P = c.PE_size;
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
-    const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
-    thread_local std::vector<unsigned char> tmp, peer;
+    const std::vector<int> order = caller_first(c);
+    thread_local std::vector<unsigned char> peer;
+    if (P > 1) peer.resize(*std::max_element(bytes, bytes + M));
+    const bool ok = many_host_fold(  // the own copies: :79-81
+        M, accs, sources, bytes, nelems, P > 1 ? peer.data() : nullptr, order.data(), P,
+        [&](void *dst, const void *src, size_t n, int pe) { c.ops.getmem(dst, src, n, pe); },
+        [&](void *a, const void *in, size_t n, int) { return osgpu::host_fold(c.type, c.op, a, in, n); },
+        [&] {
+            // long double: bytes 10..15 of every written slot are zero on every
+            // path (longdouble.hip).  The folds write them so; a set of one PE
+            // has no fold, and the copy would carry the source's padding along
+            if (P == 1)
+                for (int i = 0; i < M; i++) zero_ld_padding(c.type, accs[i], nelems[i]);
+            barrier(c);  // :82 -- every source is ready
+        });
+    if (!ok) fatal(c.name, "host fold: type %d op %d", c.type, c.op);
+    barrier(c);  // :113 -- every peer is done reading my sources
+}
+
+// One array: c.nreduce elements at `mine` (c.source, or a block of it) into
+// c.target; `overlap`: the target shares bytes with my source (:114-119).
+void run_host_fold(const Call &c, const void *mine, bool overlap)
+{
+    thread_local std::vector<unsigned char> tmp;
     if (overlap) tmp.resize(c.nbytes);
     void *acc = overlap ? (void *) tmp.data() : c.target;
-    memcpy(acc, c.source, c.nbytes);  // :79-81
-    // long double: bytes 10..15 of every written slot are zero on every path
-    // (longdouble.hip).  The folds below write them so; a set of one PE has
-    // no fold, and the copy would carry the source's padding into the target
-    if (c.type == osgpu::T_LONGDOUBLE && P == 1)
-        for (size_t i = 0; i < (size_t) c.nreduce; i++) memset((char *) acc + 16 * i + 10, 0, 6);
-    barrier(c);                       // :82 -- every source is ready
-    peer.resize(c.nbytes);
-    for (int k = 1; k < P; k++) {     // order[0] is this PE
-        c.ops.getmem(peer.data(), c.source, c.nbytes, order[k]);
-        if (!osgpu::host_fold(c.type, c.op, acc, peer.data(), (size_t) c.nreduce))
-            fatal(c.name, "host fold: type %d op %d", c.type, c.op);
-    }
-    barrier(c);                       // :113 -- every peer is done reading my source
-    if (overlap) memcpy(c.target, acc, c.nbytes);  // :114-119
+    const size_t n = (size_t) c.nreduce;
+    host_fold_table(c, 1, &acc, &mine, &c.nbytes, &n);
+    if (overlap) memcpy(c.target, acc, c.nbytes);
 }
 
 void to_all(const char *name, int type, int op, void *target, void *source, int nreduce,
@@ -692,31 +826,18 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
 {
     (void) pWrk;  // the combine needs no bounce buffer: peers are read directly
     Call c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
-    c.target = target;
-    c.source = source;
-    c.nreduce = nreduce;
-    if (nreduce <= 0) {  // nothing to combine; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    if (!begin_call(c, name, type, op, target, source, nreduce, PE_start, logPE_stride, PE_size,
+                    pSync, nreduce <= 0))
         return;
-    }
     c.nbytes = type_size(type) * (size_t) nreduce;  // no int overflow (cf. :44)
 
-    int dt = -1, ds = -1;
-    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
-    if (kt != ks)
-        fatal(name, "target and source must both be device or both be host memory");
-    if (kt == MEM_HOST) {
+    int dt = -1;
+    const Array arrays[] = {{target, c.nbytes}, {source, c.nbytes}};
+    if (arrays_kind(c, arrays, 2, &dt) == MEM_HOST) {
         const int hp = host_path();
-        require_host_heaps(c);
-        // a size every member shares: all of them take the same path
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && (size_t) (c.PE_size - 1) * c.nbytes <= fold_lim &&
-            osgpu::host_fold_supported(type, op)) {
-            run_host_fold(c);
+        if (host_route_fold(c, hp, (size_t) (c.PE_size - 1) * c.nbytes,
+                            osgpu::host_fold_supported(type, op), nullptr)) {
+            run_host_fold(c, source, ranges_overlap(target, c.nbytes, source, c.nbytes));
             return;
         }
         StageSet *S = hp == OSGPU_HOST_GETMEM ? nullptr : stage_setup(c);
@@ -764,7 +885,7 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
             run_team_push(c, srcs, dsts, idx, *G);
         else
             run_team(c, srcs, dsts, idx, remote);
-    } else if (member_sources(c, srcs)) {
+    } else if (symmetric_ptrs(c, c.source, c.nbytes, srcs)) {  // both pull forms
         if (fused_eligible(c, false) && (S = sync_setup(c)))
             run_fused(c, *S, srcs, dsts, false);
         else
@@ -797,104 +918,29 @@ void to_all(const char *name, int type, int op, void *target, void *source, int 
 // unless the block is a multiple of 16 bytes: launch_combine_shifted.
 void run_rs_pull(const Call &c, const RsBlock &b)
 {
-    hipStream_t st = pe_stream(c.name, c.me);
     const int P = c.PE_size;
-    int seg = -1;
-    size_t off = 0;
-    bool ok = heap_locate(c.me, c.source, b.source_bytes, &seg, &off);
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
     std::vector<const void *> srcs(P);  // block m of every source, in this PE's fold order
-    for (int k = 0; ok && k < P; k++) {
-        char *p = nullptr;
-        ok = heap_peer(order[k], seg, off, b.source_bytes, &p);
-        srcs[k] = ok ? p + b.offset : nullptr;
-    }
-    if (!ok)
-        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
-                      "(osgpu_heap_create / osgpu_heap_register) and the whole %zu-byte source "
-                      "inside it", b.source_bytes);
-    t_last_path = OSGPU_RAN_PULL;
+    if (!fold_sources(c, caller_first(c), c.source, b.source_bytes, b.offset, srcs.data()))
+        no_device_heap(c, "source", b.source_bytes);
     DBG("%s PE %d: pull path, block %d of %d, %zu bytes at %zu", c.name, c.me, c.index_of(c.me), P,
         b.bytes, b.offset);
-    entry_sync(c.name, st);
-    barrier(c);  // every source is ready
     const bool overlap = P > 1 && ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
-    const DeviceOut out(c, c.target, overlap, b.bytes);
-    launched(c.name, "combine launch",
-             osgpu::launch_combine_shifted(c.type, c.op, out.out, srcs.data(), P,
-                                           (size_t) c.nreduce, st));
-    stream_wait(c.name, st);
-    barrier(c);  // peers are done reading my source
-    out.finish(b.bytes, st);
+    run_pull(c, b.bytes, overlap, [&](void *out, hipStream_t st) {
+        launched(c.name, "combine launch",
+                 osgpu::launch_combine_shifted(c.type, c.op, out, srcs.data(), P,
+                                               (size_t) c.nreduce, st));
+    });
 }
 
-// Host heaps, what the caller pulls ((P - 1) blocks) at most
-// host_fold_max_bytes(): run_host_fold over block m, one shmem_getmem of the
-// block per peer.  No peer, no peer buffer.
-void run_rs_host_fold(const Call &c, const RsBlock &b)
-{
-    t_last_path = OSGPU_RAN_HOST_FOLD;
-    const int P = c.PE_size;
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
-    const bool overlap = ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
-    thread_local std::vector<unsigned char> tmp, peer;
-    if (overlap) tmp.resize(b.bytes);
-    if (P > 1) peer.resize(b.bytes);
-    void *acc = overlap ? (void *) tmp.data() : c.target;
-    const bool ok = rs_host_fold(
-        b, c.source, acc, P > 1 ? peer.data() : nullptr, order.data(), P, (size_t) c.nreduce,
-        [&](void *dst, const void *src, size_t n, int pe) { c.ops.getmem(dst, src, n, pe); },
-        [&](void *a, const void *in, size_t n) { return osgpu::host_fold(c.type, c.op, a, in, n); },
-        [&] {
-            // long double at P == 1: zero padding, as run_host_fold
-            if (c.type == osgpu::T_LONGDOUBLE && P == 1)
-                for (size_t i = 0; i < (size_t) c.nreduce; i++)
-                    memset((char *) acc + 16 * i + 10, 0, 6);
-            barrier(c);  // every source is ready
-        });
-    if (!ok) fatal(c.name, "host fold: type %d op %d", c.type, c.op);
-    barrier(c);  // every peer is done reading my source
-    if (overlap) memcpy(c.target, acc, b.bytes);
-}
-
-// Host heaps above that: run_host restricted to block m, in chunks of
-// host_chunk_bytes().
+// Host heaps above the host fold's limit: run_host restricted to block m.
 void run_rs_host(const Call &c, const RsBlock &b)
 {
-    hipStream_t st = pe_stream(c.name, c.me);
-    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
-    const int P = c.PE_size;
     t_last_path = OSGPU_RAN_GETMEM;
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
-    const size_t chunk = rs_chunk_elems(host_chunk_bytes(), s, N), cb = chunk * s;
-    char *dbuf = (char *) device_scratch(c.name, c.me, cb * (P + 1));
-    char *hbuf = (char *) host_stage(c.name, c.me, cb * (P + 1));
-    const bool overlap = P > 1 && ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
+    const bool overlap =
+        c.PE_size > 1 && ranges_overlap(c.target, b.bytes, c.source, b.source_bytes);
     HostTmp result(c, c.target, overlap, b.bytes);
-    std::vector<const void *> srcs(P);
-    for (int k = 0; k < P; k++) srcs[k] = dbuf + (size_t) k * cb;
-    const char *mine = (const char *) c.source + b.offset;
-
     barrier(c);  // every source is ready
-    for (size_t off = 0; off < N; off += chunk) {
-        const size_t n = N - off < chunk ? N - off : chunk, nb = n * s;
-        for (int k = 0; k < P; k++) {
-            char *hk = hbuf + (size_t) k * cb;
-            if (order[k] == c.me) memcpy(hk, mine + off * s, nb);
-            else c.ops.getmem(hk, mine + off * s, nb, order[k]);
-            HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
-        }
-        // (a slot of cb bytes need not be a multiple of 16: the slots' phases may differ)
-        char *dout = dbuf + (size_t) P * cb, *hout = hbuf + (size_t) P * cb;
-        launched(c.name, "combine launch",
-                 osgpu::launch_combine_shifted(c.type, c.op, dout, srcs.data(), P, n, st));
-        HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
-        stream_wait(c.name, st);
-        memcpy(result.out + off * s, hout, nb);
-    }
+    getmem_chunks(c, caller_first(c), b.offset, osgpu::launch_combine_shifted, result.out);
     barrier(c);  // every peer is done reading my source
     result.finish(b.bytes);
 }
@@ -902,43 +948,27 @@ void run_rs_host(const Call &c, const RsBlock &b)
 void reduce_scatter(const char *name, int type, int op, void *target, const void *source,
                     int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
 {
-    if (!(has_op(type, op) || has_ext_op(type, op)))
-        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_scatter)",
-              type, op);
+    require_reduction(name, type, op, "osgpu_has_reduce_scatter");
     Call c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
-    c.target = target;
-    c.source = const_cast<void *>(source);
-    c.nreduce = nreduce;
-    if (nreduce <= 0) {  // nothing to combine; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    if (!begin_call(c, name, type, op, target, source, nreduce, PE_start, logPE_stride, PE_size,
+                    pSync, nreduce <= 0))
         return;
-    }
     RsBlock b;
     if (!rs_block(type_size(type), nreduce, PE_size, c.index_of(c.me), &b))
         fatal(name, "%d blocks of %d elements do not fit the address space", PE_size, nreduce);
     c.nbytes = b.bytes;
 
-    int dt = -1, ds = -1;
-    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
-    if (kt != ks)
-        fatal(name, "target and source must both be device or both be host memory");
-    if (kt == MEM_HOST) {
-        const int hp = host_path();
-        require_host_heaps(c);
-        // a size every member shares: all of them take the same path
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bytes <= fold_lim &&
-            osgpu::host_fold_supported(type, op)) {
-            run_rs_host_fold(c, b);
-            return;
-        }
-        if (hp == OSGPU_HOST_STAGED)
-            DBG("%s PE %d: no STAGED form of the reduce-scatter, taking GETMEM", name, c.me);
-        run_rs_host(c, b);
+    int dt = -1;
+    const Array arrays[] = {{target, b.bytes}, {source, b.source_bytes}};
+    if (arrays_kind(c, arrays, 2, &dt) == MEM_HOST) {
+        // the host fold: run_host_fold over block m, one shmem_getmem of the
+        // block per peer ((P - 1) blocks pulled)
+        if (host_route_fold(c, host_path(), b.pulled_bytes, osgpu::host_fold_supported(type, op),
+                            "the reduce-scatter"))
+            run_host_fold(c, (const char *) source + b.offset,
+                          ranges_overlap(target, b.bytes, source, b.source_bytes));
+        else
+            run_rs_host(c, b);
         return;
     }
     const DeviceGuard on_device(name, dt);
@@ -987,24 +1017,13 @@ void run_many_pull(const Call &c, const Many &m)
 {
     hipStream_t st = pe_stream(c.name, c.me);
     const int P = c.PE_size, M = m.count();
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    const std::vector<int> order = caller_first(c);
     // every entry's source on every member, in this PE's fold order
     std::vector<const void *> srcs((size_t) M * P);
     std::vector<const void *const *> rows(M);
     for (int i = 0; i < M; i++) {
-        int seg = -1;
-        size_t off = 0;
-        bool ok = heap_locate(c.me, m.source[i], m.bytes[i], &seg, &off);
-        for (int k = 0; ok && k < P; k++) {
-            char *p = nullptr;
-            ok = heap_peer(order[k], seg, off, m.bytes[i], &p);
-            srcs[(size_t) i * P + k] = p;
-        }
-        if (!ok)
-            fatal(c.name, "device-resident arguments need every active PE's device heap registered "
-                          "(osgpu_heap_create / osgpu_heap_register) and every source inside it "
-                          "(entry %d of the non-empty ones, %zu bytes)", i, m.bytes[i]);
+        if (!fold_sources(c, order, m.source[i], m.bytes[i], 0, &srcs[(size_t) i * P]))
+            no_device_heap(c, "source of a non-empty entry", m.bytes[i]);
         rows[i] = &srcs[(size_t) i * P];
     }
     t_last_path = OSGPU_RAN_PULL;
@@ -1033,31 +1052,14 @@ void run_many_pull(const Call &c, const Many &m)
 
 void run_many_host_fold(const Call &c, const Many &m)
 {
-    t_last_path = OSGPU_RAN_HOST_FOLD;
-    const int P = c.PE_size, M = m.count();
-    std::vector<int> order(P);
-    fold_order(c.me, c.PE_start, c.step, P, order.data());
+    const int M = m.count();
     // (the host fold copies its own source first, so any overlap takes a temporary, as run_host_fold)
     const ManyTmp tmp(m, true);
-    thread_local std::vector<unsigned char> tbuf, peer;
+    thread_local std::vector<unsigned char> tbuf;
     tbuf.resize(tmp.bytes);
-    if (P > 1) peer.resize(*std::max_element(m.bytes.begin(), m.bytes.end()));
     std::vector<void *> accs(M);
     for (int i = 0; i < M; i++) accs[i] = tmp.used(i) ? (void *) (tbuf.data() + tmp.off[i]) : m.target[i];
-    const bool ok = many_host_fold(
-        M, accs.data(), m.source.data(), m.bytes.data(), m.n.data(), P > 1 ? peer.data() : nullptr,
-        order.data(), P,
-        [&](void *dst, const void *src, size_t n, int pe) { c.ops.getmem(dst, src, n, pe); },
-        [&](void *a, const void *in, size_t n, int) { return osgpu::host_fold(c.type, c.op, a, in, n); },
-        [&] {
-            // long double at P == 1: zero padding, as run_host_fold
-            if (c.type == osgpu::T_LONGDOUBLE && P == 1)
-                for (int i = 0; i < M; i++)
-                    for (size_t k = 0; k < m.n[i]; k++) memset((char *) accs[i] + 16 * k + 10, 0, 6);
-            barrier(c);  // every source is ready
-        });
-    if (!ok) fatal(c.name, "host fold: type %d op %d", c.type, c.op);
-    barrier(c);  // every peer is done reading my sources
+    host_fold_table(c, M, accs.data(), m.source.data(), m.bytes.data(), m.n.data());
     for (int i = 0; i < M; i++)
         if (tmp.used(i)) memcpy(m.target[i], accs[i], m.bytes[i]);
 }
@@ -1068,6 +1070,7 @@ void run_many_host(const Call &c, const Many &m)
     const int M = m.count();
     const ManyTmp tmp(m, c.PE_size > 1);
     std::vector<unsigned char> tbuf(tmp.bytes);
+    const std::vector<int> order = caller_first(c);
     barrier(c);  // every source is ready
     for (int i = 0; i < M; i++) {
         Call e = c;
@@ -1075,7 +1078,8 @@ void run_many_host(const Call &c, const Many &m)
         e.source = const_cast<void *>(m.source[i]);
         e.nreduce = (int) m.n[i];
         e.nbytes = m.bytes[i];
-        host_chunks(e, tmp.used(i) ? (char *) tbuf.data() + tmp.off[i] : (char *) m.target[i]);
+        getmem_chunks(e, order, 0, osgpu::launch_combine,
+                      tmp.used(i) ? (char *) tbuf.data() + tmp.off[i] : (char *) m.target[i]);
     }
     barrier(c);  // every peer is done reading my sources
     for (int i = 0; i < M; i++)
@@ -1086,16 +1090,10 @@ void reduce_many(const char *name, int type, int op, int count, void *const *tar
                  const void *const *sources, const int *nreduces, int PE_start, int logPE_stride,
                  int PE_size, long *pSync)
 {
-    if (!(has_op(type, op) || has_ext_op(type, op)))
-        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_many)", type,
-              op);
+    require_reduction(name, type, op, "osgpu_has_reduce_many");
     if (count < 0) fatal(name, "count %d is negative", count);
     if (count > 0 && (!targets || !sources || !nreduces))
         fatal(name, "a table of %d entries needs targets, sources and nreduces", count);
-    Call c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
     Many m;
     const size_t s = type_size(type);
     for (int i = 0; i < count; i++) {
@@ -1107,11 +1105,10 @@ void reduce_many(const char *name, int type, int op, int count, void *const *tar
         m.total += m.bytes.back();
     }
     const int M = m.count();
-    if (M == 0) {  // nothing to combine; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    Call c;  // (the set, type and op; the arrays are the table's)
+    if (!begin_call(c, name, type, op, nullptr, nullptr, 0, PE_start, logPE_stride, PE_size, pSync,
+                    M == 0))
         return;
-    }
     {   // the table's contract, before the first barrier
         std::vector<uintptr_t> ta(M), sa(M);
         for (int i = 0; i < M; i++) ta[i] = (uintptr_t) m.target[i], sa[i] = (uintptr_t) m.source[i];
@@ -1121,30 +1118,16 @@ void reduce_many(const char *name, int type, int op, int count, void *const *tar
             fatal(name, "the target of one entry overlaps the target or source of another "
                         "(non-empty entries %d and %d)", bad, other);
     }
+    std::vector<Array> arrays;  // the first target first: its device is the call's
+    for (int i = 0; i < M; i++) arrays.push_back({m.target[i], m.bytes[i]});
+    for (int i = 0; i < M; i++) arrays.push_back({m.source[i], m.bytes[i]});
     int dev = -1;
-    const MemKind kind = mem_kind(m.target[0], &dev);
-    // (an array inside my registered device heap needs no pointer query)
-    auto kind_of = [&](const void *p, size_t n) {
-        int seg = -1;
-        size_t off = 0;
-        return heap_locate(c.me, p, n, &seg, &off) ? MEM_DEVICE : mem_kind(p, nullptr);
-    };
-    for (int i = 0; i < M; i++)
-        if (kind_of(m.source[i], m.bytes[i]) != kind || (i && kind_of(m.target[i], m.bytes[i]) != kind))
-            fatal(name, "every target and source must be device memory, or every one host memory");
-    if (kind == MEM_HOST) {
-        const int hp = host_path();
-        require_host_heaps(c);
-        // a size every member shares: all of them take the same path
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && (size_t) (c.PE_size - 1) * m.total <= fold_lim &&
-            osgpu::host_fold_supported(type, op)) {
+    if (arrays_kind(c, arrays.data(), arrays.size(), &dev, true) == MEM_HOST) {
+        if (host_route_fold(c, host_path(), (size_t) (c.PE_size - 1) * m.total,
+                            osgpu::host_fold_supported(type, op), "the batched reduce"))
             run_many_host_fold(c, m);
-            return;
-        }
-        if (hp == OSGPU_HOST_STAGED)
-            DBG("%s PE %d: no STAGED form of the batched reduce, taking GETMEM", name, c.me);
-        run_many_host(c, m);
+        else
+            run_many_host(c, m);
         return;
     }
     const DeviceGuard on_device(name, dev);
@@ -1170,13 +1153,6 @@ static_assert((int) SCAN_T_SHORT == (int) OSGPU_T_SHORT &&
                   (int) SCAN_OP_SUM == (int) OSGPU_OP_SUM && (int) SCAN_OP_XOR == (int) OSGPU_OP_XOR &&
                   (int) SCAN_OP_MIN == (int) OSGPU_OP_MIN,
               "scan_host.hpp repeats the codes of osgpu_reduce.h");
-
-// long double: bytes 10..15 of every slot a COPY wrote are zero, as after a fold
-void zero_ld_padding(const Call &c, void *p)
-{
-    if (c.type != osgpu::T_LONGDOUBLE) return;
-    for (size_t i = 0; i < (size_t) c.nreduce; i++) memset((char *) p + 16 * i + 10, 0, 6);
-}
 
 // TEAM of the scan and the uniform reduce (`what`): every member launches the
 // kernel, launch(P, dsts, srcs, n, stream), over its own contiguous shard of
@@ -1215,57 +1191,36 @@ void run_team_shards(const Call &c, const std::vector<const void *> &srcs,
 // member m takes K = scan_prefix_len, the uniform reduce K = PE_size.
 void run_prefix_pull(const Call &c, int K)
 {
-    hipStream_t st = pe_stream(c.name, c.me);
-    int seg = -1;
-    size_t off = 0;
-    bool ok = heap_locate(c.me, c.source, c.nbytes, &seg, &off);
     std::vector<const void *> srcs(K);
-    for (int k = 0, pe = c.PE_start; ok && k < K; k++, pe += c.step) {
-        char *p = nullptr;
-        ok = heap_peer(pe, seg, off, c.nbytes, &p);
-        srcs[k] = p;
-    }
-    if (!ok)
-        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
-                      "(osgpu_heap_create / osgpu_heap_register) and the %zu-byte source inside it",
-              c.nbytes);
-    t_last_path = OSGPU_RAN_PULL;
+    if (!fold_sources(c, ascending(c, K), c.source, c.nbytes, 0, srcs.data()))
+        no_device_heap(c, "source", c.nbytes);
     DBG("%s PE %d: pull over the first %d members, ascending", c.name, c.me, K);
-    entry_sync(c.name, st);
-    barrier(c);  // every source is ready
     // (member 0's identity too: peers read the source its target may overlap)
     const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
-    const DeviceOut out(c, c.target, overlap, c.nbytes);
-    if (K == 0)
-        launched(c.name, "identity fill launch",
-                 osgpu::launch_scan_fill(c.type, c.op, out.out, (size_t) c.nreduce, st));
-    else
-        launched(c.name, "combine launch",
-                 osgpu::launch_combine_shifted(c.type, c.op, out.out, srcs.data(), K,
-                                               (size_t) c.nreduce, st));
-    stream_wait(c.name, st);
-    barrier(c);  // peers are done reading my source
-    out.finish(c.nbytes, st);
+    run_pull(c, c.nbytes, overlap, [&](void *out, hipStream_t st) {
+        if (K == 0)
+            launched(c.name, "identity fill launch",
+                     osgpu::launch_scan_fill(c.type, c.op, out, (size_t) c.nreduce, st));
+        else
+            launched(c.name, "combine launch",
+                     osgpu::launch_combine_shifted(c.type, c.op, out, srcs.data(), K,
+                                                   (size_t) c.nreduce, st));
+    });
 }
 
-void run_scan_pull(const Call &c, int excl)
+// member j's bytes [off, off + nb) of the symmetric host array `array` as
+// this member sees them: its own array, or one getmem into `buf`
+const void *host_input(const Coll &c, const void *array, int j, size_t off, size_t nb, void *buf)
 {
-    run_prefix_pull(c, scan_prefix_len(c.index_of(c.me), excl));
-}
-
-// member j's source as member m sees it on a host heap: its own array, or
-// one getmem of `nb` bytes from `off` into `buf`
-const void *scan_host_input(const Call &c, int j, size_t off, size_t nb, void *buf)
-{
-    const int pe = c.PE_start + j * c.step;
-    const char *src = (const char *) c.source + off;
+    const int pe = c.pe_at(j);
+    const char *src = (const char *) array + off;
     if (pe == c.me) return src;
     c.ops.getmem(buf, src, nb, pe);
     return buf;
 }
 
-// Host heaps, the last member's pull ((P - 1) arrays) at most
-// host_fold_max_bytes(): the fold of the first K members on this PE's thread,
+// Host heaps, the last member's pull ((P - 1) arrays) within the host fold's
+// limit: the fold of the first K members on this PE's thread,
 // ascending -- the caller's own source in its place in the order -- one
 // getmem of the whole array per peer it folds.
 void run_prefix_host_fold(const Call &c, int K)
@@ -1281,10 +1236,11 @@ void run_prefix_host_fold(const Call &c, int K)
         if (!scan_fill_identity(c.type, c.op, acc, (size_t) c.nreduce))
             fatal(c.name, "no identity for type %d op %d", c.type, c.op);
     } else {
-        memmove(acc, scan_host_input(c, 0, 0, c.nbytes, peer.data()), c.nbytes);
-        if (K == 1) zero_ld_padding(c, acc);
+        memmove(acc, host_input(c, c.source, 0, 0, c.nbytes, peer.data()), c.nbytes);
+        if (K == 1) zero_ld_padding(c.type, acc, (size_t) c.nreduce);
         for (int j = 1; j < K; j++)
-            if (!osgpu::host_fold(c.type, c.op, acc, scan_host_input(c, j, 0, c.nbytes, peer.data()),
+            if (!osgpu::host_fold(c.type, c.op, acc,
+                                  host_input(c, c.source, j, 0, c.nbytes, peer.data()),
                                   (size_t) c.nreduce))
                 fatal(c.name, "host fold: type %d op %d", c.type, c.op);
     }
@@ -1292,98 +1248,47 @@ void run_prefix_host_fold(const Call &c, int K)
     if (overlap) memcpy(c.target, acc, c.nbytes);
 }
 
-void run_scan_host_fold(const Call &c, int excl)
-{
-    run_prefix_host_fold(c, scan_prefix_len(c.index_of(c.me), excl));
-}
-
 // Host heaps above that: the K inputs pulled in chunks of host_chunk_bytes()
 // into pinned staging, combined on the GPU.  Member 0 of an exclusive scan
 // (K == 0) writes the identity on the host.
 void run_prefix_host(const Call &c, int K)
 {
-    hipStream_t st = pe_stream(c.name, c.me);
-    const size_t s = type_size(c.type), N = (size_t) c.nreduce;
     t_last_path = OSGPU_RAN_GETMEM;
     const bool overlap = ranges_overlap(c.target, c.nbytes, c.source, c.nbytes);
     HostTmp result(c, c.target, overlap, c.nbytes);
     barrier(c);  // every source is ready
-    if (K == 0) {
-        if (!scan_fill_identity(c.type, c.op, result.out, N))
-            fatal(c.name, "no identity for type %d op %d", c.type, c.op);
-    } else {
-        const size_t chunk = scan_chunk_elems(host_chunk_bytes(), s, N), cb = chunk * s;
-        char *dbuf = (char *) device_scratch(c.name, c.me, cb * (K + 1));
-        char *hbuf = (char *) host_stage(c.name, c.me, cb * (K + 1));
-        std::vector<const void *> srcs(K);
-        for (int k = 0; k < K; k++) srcs[k] = dbuf + (size_t) k * cb;
-        scan_for_chunks(N, chunk, [&](size_t off, size_t n) {
-            const size_t nb = n * s;
-            for (int k = 0; k < K; k++) {
-                char *hk = hbuf + (size_t) k * cb;
-                const void *in = scan_host_input(c, k, off * s, nb, hk);
-                if (in != hk) memcpy(hk, in, nb);
-                HIPCHK(c.name, hipMemcpyAsync((void *) srcs[k], hk, nb, hipMemcpyHostToDevice, st));
-            }
-            // (a slot of cb bytes need not be a multiple of 16: the slots' phases may differ)
-            char *dout = dbuf + (size_t) K * cb, *hout = hbuf + (size_t) K * cb;
-            launched(c.name, "combine launch",
-                     osgpu::launch_combine_shifted(c.type, c.op, dout, srcs.data(), K, n, st));
-            HIPCHK(c.name, hipMemcpyAsync(hout, dout, nb, hipMemcpyDeviceToHost, st));
-            stream_wait(c.name, st);
-            memcpy(result.out + off * s, hout, nb);
-        });
-    }
+    if (K > 0)
+        getmem_chunks(c, ascending(c, K), 0, osgpu::launch_combine_shifted, result.out);
+    else if (!scan_fill_identity(c.type, c.op, result.out, (size_t) c.nreduce))
+        fatal(c.name, "no identity for type %d op %d", c.type, c.op);
     barrier(c);  // every peer is done reading my source
     result.finish(c.nbytes);
-}
-
-void run_scan_host(const Call &c, int excl)
-{
-    run_prefix_host(c, scan_prefix_len(c.index_of(c.me), excl));
 }
 
 void scan(const char *name, int type, int op, int exclusive, void *target, const void *source,
           int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
 {
-    if (!(has_op(type, op) || has_ext_op(type, op)))
-        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_scan)", type, op);
+    require_reduction(name, type, op, "osgpu_has_scan");
     if (exclusive != 0 && exclusive != 1)
         fatal(name, "exclusive is %d: 0 (inclusive) or 1 (exclusive)", exclusive);
     Call c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
-    c.target = target;
-    c.source = const_cast<void *>(source);
-    c.nreduce = nreduce;
-    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    if (!begin_call(c, name, type, op, target, source, nreduce, PE_start, logPE_stride, PE_size,
+                    pSync, nreduce <= 0))
         return;
-    }
     ScanBytes b;
     if (!scan_bytes(type_size(type), nreduce, PE_size, c.index_of(c.me), exclusive, &b))
         fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
     c.nbytes = b.bytes;
+    const int K = scan_prefix_len(c.index_of(c.me), exclusive);  // the members I fold
 
-    int dt = -1, ds = -1;
-    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
-    if (kt != ks)
-        fatal(name, "target and source must both be device or both be host memory");
-    if (kt == MEM_HOST) {
-        const int hp = host_path();
-        require_host_heaps(c);
-        // a size every member shares: all of them take the same path
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
-            osgpu::host_fold_supported(type, op)) {
-            run_scan_host_fold(c, exclusive);
-            return;
-        }
-        if (hp == OSGPU_HOST_STAGED)
-            DBG("%s PE %d: no STAGED form of the scan, taking GETMEM", name, c.me);
-        run_scan_host(c, exclusive);
+    int dt = -1;
+    const Array arrays[] = {{target, b.bytes}, {source, b.bytes}};
+    if (arrays_kind(c, arrays, 2, &dt) == MEM_HOST) {
+        if (host_route_fold(c, host_path(), b.pulled_bound, osgpu::host_fold_supported(type, op),
+                            "the scan"))
+            run_prefix_host_fold(c, K);
+        else
+            run_prefix_host(c, K);
         return;
     }
     const DeviceGuard on_device(name, dt);
@@ -1400,7 +1305,7 @@ void scan(const char *name, int type, int op, int exclusive, void *target, const
                             return osgpu::launch_team_scan(type, op, exclusive, P, d, sr, n, st);
                         });
     else
-        run_scan_pull(c, exclusive);
+        run_prefix_pull(c, K);
 }
 
 // ------------------------------------------------- uniform reduce-to-all
@@ -1410,52 +1315,30 @@ void scan(const char *name, int type, int op, int exclusive, void *target, const
 // inclusive scan -- so all targets hold the same bytes.  Paths: device heaps
 // the owner-computes uniform kernel (launch_team_uniform, long double
 // included) or the pull form; host heaps the host fold and GETMEM.  The pull
-// and host forms are the scan's over K = PE_size members: never
+// and host forms are the scan's (run_prefix_*) over K = PE_size members: never
 // osgpu_fold_order's caller-first order.  No FUSED, STAGED, RCCL or push form.
-
-void run_uniform_pull(const Call &c) { run_prefix_pull(c, c.PE_size); }
-void run_uniform_host_fold(const Call &c) { run_prefix_host_fold(c, c.PE_size); }
-void run_uniform_host(const Call &c) { run_prefix_host(c, c.PE_size); }
 
 void reduce_uniform(const char *name, int type, int op, void *target, const void *source,
                     int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
 {
-    if (!(has_op(type, op) || has_ext_op(type, op)))
-        fatal(name, "type %d op %d is not a reduction of this library (osgpu_has_reduce_uniform)",
-              type, op);
+    require_reduction(name, type, op, "osgpu_has_reduce_uniform");
     Call c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
-    c.target = target;
-    c.source = const_cast<void *>(source);
-    c.nreduce = nreduce;
-    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    if (!begin_call(c, name, type, op, target, source, nreduce, PE_start, logPE_stride, PE_size,
+                    pSync, nreduce <= 0))
         return;
-    }
     ScanBytes b;  // the inclusive scan's byte counts: every member folds what its last one does
     if (!scan_bytes(type_size(type), nreduce, PE_size, c.index_of(c.me), 0, &b))
         fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
     c.nbytes = b.bytes;
 
-    int dt = -1, ds = -1;
-    MemKind kt = mem_kind(target, &dt), ks = mem_kind(source, &ds);
-    if (kt != ks)
-        fatal(name, "target and source must both be device or both be host memory");
-    if (kt == MEM_HOST) {
-        const int hp = host_path();
-        require_host_heaps(c);
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
-            osgpu::host_fold_supported(type, op)) {
-            run_uniform_host_fold(c);
-            return;
-        }
-        if (hp == OSGPU_HOST_STAGED)
-            DBG("%s PE %d: no STAGED form of the uniform reduce, taking GETMEM", name, c.me);
-        run_uniform_host(c);
+    int dt = -1;
+    const Array arrays[] = {{target, b.bytes}, {source, b.bytes}};
+    if (arrays_kind(c, arrays, 2, &dt) == MEM_HOST) {
+        if (host_route_fold(c, host_path(), b.pulled_bound, osgpu::host_fold_supported(type, op),
+                            "the uniform reduce"))
+            run_prefix_host_fold(c, PE_size);
+        else
+            run_prefix_host(c, PE_size);
         return;
     }
     const DeviceGuard on_device(name, dt);
@@ -1471,7 +1354,7 @@ void reduce_uniform(const char *name, int type, int op, void *target, const void
                             return osgpu::launch_team_uniform(type, op, P, d, sr, n, st);
                         });
     else
-        run_uniform_pull(c);
+        run_prefix_pull(c, PE_size);
 }
 
 // ------------------------------------------- max / min with location
@@ -1490,18 +1373,6 @@ struct LocCall : Call {
     size_t lbytes = 0;
     int member_pe(int j) const { return pe_at(j); }
 };
-
-// `p`, nbytes long, in my registered heap: every member's copy of it
-bool symmetric_ptrs(const Coll &c, const void *p, size_t nbytes, std::vector<char *> &out)
-{
-    int seg = -1;
-    size_t off = 0;
-    if (!heap_locate(c.me, p, nbytes, &seg, &off)) return false;
-    out.resize(c.PE_size);
-    for (int i = 0, pe = c.PE_start; i < c.PE_size; i++, pe += c.step)
-        if (!heap_peer(pe, seg, off, nbytes, &out[i])) return false;
-    return true;
-}
 
 // TEAM: all four arrays (three without index sources) symmetric, nothing
 // overlapping, 2..8 members.  Every member folds its shard of all targets.
@@ -1555,9 +1426,7 @@ void run_loc_pull(const LocCall &c)
     std::vector<char *> vs, ls;
     if (!symmetric_ptrs(c, c.source, c.nbytes, vs) ||
         (c.loc_source && !symmetric_ptrs(c, c.loc_source, c.lbytes, ls)))
-        fatal(c.name, "device-resident arguments need every active PE's device heap registered "
-                      "(osgpu_heap_create / osgpu_heap_register) and the %zu-byte source%s inside it",
-              c.nbytes, c.loc_source ? " and the index source" : "");
+        no_device_heap(c, c.loc_source ? "source (and its index source)" : "source", c.nbytes);
     t_last_path = OSGPU_RAN_PULL;
     DBG("%s PE %d: pull over %d members, ascending", c.name, c.me, P);
     entry_sync(c.name, st);
@@ -1590,18 +1459,6 @@ void run_loc_pull(const LocCall &c)
     if (ov || ol) stream_wait(c.name, st);
 }
 
-// member j's bytes [off, off + nb) of the symmetric host array `mine` as this
-// member sees them: its own array, or one getmem into `buf`
-const void *loc_host_input(const LocCall &c, const void *mine, int j, size_t off, size_t nb,
-                           void *buf)
-{
-    const int pe = c.member_pe(j);
-    const char *src = (const char *) mine + off;
-    if (pe == c.me) return src;
-    c.ops.getmem(buf, src, nb, pe);
-    return buf;
-}
-
 // Host heaps, small calls: the fold on this PE's thread, ascending, one
 // getmem of each whole array per peer.
 void run_loc_host_fold(const LocCall &c)
@@ -1619,15 +1476,15 @@ void run_loc_host_fold(const LocCall &c)
     void *accv = ov ? (void *) tv.data() : c.target;
     int *accl = ol ? (int *) tl.data() : c.loc_target;
     barrier(c);  // every source is ready
-    memmove(accv, loc_host_input(c, c.source, 0, 0, c.nbytes, pv.data()), c.nbytes);
+    memmove(accv, host_input(c, c.source, 0, 0, c.nbytes, pv.data()), c.nbytes);
     if (c.loc_source)
-        memmove(accl, loc_host_input(c, c.loc_source, 0, 0, c.lbytes, pl.data()), c.lbytes);
+        memmove(accl, host_input(c, c.loc_source, 0, 0, c.lbytes, pl.data()), c.lbytes);
     else
         std::fill(accl, accl + N, c.member_pe(0));
     for (int j = 1; j < P; j++) {
-        const void *bv = loc_host_input(c, c.source, j, 0, c.nbytes, pv.data());
+        const void *bv = host_input(c, c.source, j, 0, c.nbytes, pv.data());
         const int *bl = c.loc_source
-                            ? (const int *) loc_host_input(c, c.loc_source, j, 0, c.lbytes, pl.data())
+                            ? (const int *) host_input(c, c.loc_source, j, 0, c.lbytes, pl.data())
                             : nullptr;
         if (!osgpu::host_fold_loc(c.type, c.op, accv, accl, bv, bl, c.member_pe(j), N))
             fatal(c.name, "host fold: type %d op %d", c.type, c.op);
@@ -1668,11 +1525,11 @@ void run_loc_host(const LocCall &c)
             for (int j = first, slot = 0; j < first + count; j++, k++, slot++) {
                 char *hv = hbuf + (size_t) slot * vb, *hl = hbuf + loff + (size_t) slot * lb;
                 char *dv = dbuf + (size_t) slot * vb, *dl = dbuf + loff + (size_t) slot * lb;
-                const void *in = loc_host_input(c, c.source, j, off * s, nvb, hv);
+                const void *in = host_input(c, c.source, j, off * s, nvb, hv);
                 if (in != hv) memcpy(hv, in, nvb);
                 HIPCHK(c.name, hipMemcpyAsync(dv, hv, nvb, hipMemcpyHostToDevice, st));
                 if (c.loc_source) {
-                    in = loc_host_input(c, c.loc_source, j, off * kLocIndexBytes, nlb, hl);
+                    in = host_input(c, c.loc_source, j, off * kLocIndexBytes, nlb, hl);
                     if (in != hl) memcpy(hl, in, nlb);
                     HIPCHK(c.name, hipMemcpyAsync(dl, hl, nlb, hipMemcpyHostToDevice, st));
                 }
@@ -1705,19 +1562,11 @@ void reduce_loc(const char *name, int type, int op, void *target, int *loc_targe
         fatal(name, "type %d op %d is no max / min with location of this library "
                     "(osgpu_has_reduce_loc)", type, op);
     LocCall c;
-    static_cast<Coll &>(c) = make_coll(name, PE_start, logPE_stride, PE_size, pSync);
-    c.type = type;
-    c.op = op;
-    c.target = target;
-    c.source = const_cast<void *>(source);
     c.loc_target = loc_target;
     c.loc_source = loc_source;
-    c.nreduce = nreduce;
-    if (nreduce <= 0) {  // nothing to fold; the collective still syncs
-        t_last_path = OSGPU_RAN_BARRIER_ONLY;
-        sync_only(c);
+    if (!begin_call(c, name, type, op, target, source, nreduce, PE_start, logPE_stride, PE_size,
+                    pSync, nreduce <= 0))
         return;
-    }
     LocBytes b;
     if (!loc_bytes(type_size(type), nreduce, PE_size, loc_source != nullptr, &b))
         fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
@@ -1728,24 +1577,16 @@ void reduce_loc(const char *name, int type, int op, void *target, int *loc_targe
                                              b.lbytes))
         fatal(name, "%s overlap: a value array and an index array must not share a byte", pair);
 
-    int dev = -1, d2 = -1;
-    const MemKind kind = mem_kind(target, &dev);
-    if (mem_kind(source, &d2) != kind || mem_kind(loc_target, &d2) != kind ||
-        (loc_source && mem_kind(loc_source, &d2) != kind))
-        fatal(name, "the arrays must all be device or all be host memory");
-    if (kind == MEM_HOST) {
-        const int hp = host_path();
-        require_host_heaps(c);
-        const size_t fold_lim = host_fold_max_bytes();  // 0: off
-        if (hp == OSGPU_HOST_AUTO && fold_lim > 0 && b.pulled_bound <= fold_lim &&
-            osgpu::host_fold_loc_supported(type, op)) {
+    const Array arrays[] = {
+        {target, b.vbytes}, {source, b.vbytes}, {loc_target, b.lbytes}, {loc_source, b.lbytes}};
+    int dev = -1;
+    if (arrays_kind(c, arrays, loc_source ? 4 : 3, &dev) == MEM_HOST) {
+        if (host_route_fold(c, host_path(), b.pulled_bound,
+                            osgpu::host_fold_loc_supported(type, op),
+                            "the max / min with location"))
             run_loc_host_fold(c);
-            return;
-        }
-        if (hp == OSGPU_HOST_STAGED)
-            DBG("%s PE %d: no STAGED form of the max / min with location, taking GETMEM", name,
-                c.me);
-        run_loc_host(c);
+        else
+            run_loc_host(c);
         return;
     }
     const DeviceGuard on_device(name, dev);
@@ -1866,7 +1707,7 @@ extern "C" void osgpu_reduce_scatter(int type, int op, void *target, const void 
 
 extern "C" int osgpu_has_reduce_scatter(int type, int op)
 {
-    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+    return is_reduction(type, op) ? 1 : 0;
 }
 
 // ======================================================================
@@ -1884,7 +1725,7 @@ extern "C" void osgpu_reduce_many(int type, int op, int count, void *const *targ
 
 extern "C" int osgpu_has_reduce_many(int type, int op)
 {
-    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+    return is_reduction(type, op) ? 1 : 0;
 }
 
 // ======================================================================
@@ -1902,7 +1743,7 @@ extern "C" void osgpu_scan(int type, int op, int exclusive, void *target, const 
 
 extern "C" int osgpu_has_scan(int type, int op)
 {
-    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+    return is_reduction(type, op) ? 1 : 0;
 }
 
 extern "C" int osgpu_scan_identity(int type, int op, void *elem_out)
@@ -1933,7 +1774,7 @@ extern "C" void osgpu_reduce_uniform(int type, int op, void *target, const void 
 
 extern "C" int osgpu_has_reduce_uniform(int type, int op)
 {
-    return osgpu::rt::has_op(type, op) || osgpu::rt::has_ext_op(type, op) ? 1 : 0;
+    return is_reduction(type, op) ? 1 : 0;
 }
 
 // ======================================================================

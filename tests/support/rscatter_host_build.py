@@ -1,6 +1,7 @@
 """rscatter_host_build.py -- TEST INFRASTRUCTURE: build
-tests/support/rscatter_host_check (the HIP-free block arithmetic and host-fold
-loop of osgpu_reduce_scatter, csrc/rscatter_host.hpp, with its own main) with
+tests/support/rscatter_host_check (the HIP-free block arithmetic of
+osgpu_reduce_scatter, csrc/rscatter_host.hpp, and the chunk and host-fold
+helpers it shares, scan_host.hpp and many_host.hpp, with its own main) with
 g++, plain and with ASan + UBSan, the way heap_host_build.py builds
 heap_host_check."""
 from __future__ import annotations
@@ -11,7 +12,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "..", "test-resilient-osss-ucx_amd", "csrc")
 SRCS = [os.path.join(HERE, "rscatter_host_check.cpp")]
-HDRS = [os.path.join(CSRC, "rscatter_host.hpp")]
+HDRS = [os.path.join(CSRC, h) for h in ("rscatter_host.hpp", "scan_host.hpp", "many_host.hpp")]
 PATH = os.path.join(HERE, "rscatter_host_check")
 SAN_PATH = os.path.join(HERE, "rscatter_host_check_san")
 # the runtimes linked in: a program with the shared ASan runtime refuses to

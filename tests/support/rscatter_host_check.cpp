@@ -1,6 +1,10 @@
 // rscatter_host_check.cpp -- TEST INFRASTRUCTURE: the HIP-free arithmetic of
-// osgpu_reduce_scatter's host paths (csrc/rscatter_host.hpp) with its own
-// main, built plain and with ASan + UBSan (tests/support/rscatter_host_build.py).
+// osgpu_reduce_scatter's host paths with its own main, built plain and with
+// ASan + UBSan (tests/support/rscatter_host_build.py): the block's bytes
+// (csrc/rscatter_host.hpp), and the two helpers the call shares with the
+// other collectives AS IT USES THEM -- GETMEM's chunk over the block
+// (scan_host.hpp host_chunk_elems) and the host fold over a table of one
+// entry whose source is block m of the source (many_host.hpp many_host_fold).
 // Every "heap" is a malloc of EXACTLY the source's bytes, every target and
 // peer buffer of exactly one block: a getmem or fold that leaves block m is a
 // heap-buffer-overflow.  Prints "ok".
@@ -11,7 +15,9 @@
 
 #include <vector>
 
+#include "../../test-resilient-osss-ucx_amd/csrc/many_host.hpp"
 #include "../../test-resilient-osss-ucx_amd/csrc/rscatter_host.hpp"
+#include "../../test-resilient-osss-ucx_amd/csrc/scan_host.hpp"
 
 using osgpu::rt::RsBlock;
 
@@ -43,13 +49,13 @@ static int blocks()
 
 static int chunks()
 {
-    using osgpu::rt::rs_chunk_elems;
-    CHECK(rs_chunk_elems(64 << 20, 8, 1001) == 1002);  // the block, rounded up to even
-    CHECK(rs_chunk_elems(2048, 2, 5000) == 1024);
-    CHECK(rs_chunk_elems(1, 16, 9) == 2 && rs_chunk_elems(0, 4, 1) == 2);
+    using osgpu::rt::host_chunk_elems;
+    CHECK(host_chunk_elems(64 << 20, 8, 1001) == 1002);  // the block, rounded up to even
+    CHECK(host_chunk_elems(2048, 2, 5000) == 1024);
+    CHECK(host_chunk_elems(1, 16, 9) == 2 && host_chunk_elems(0, 4, 1) == 2);
     // the chunk walk covers [0, N) exactly once, no chunk past the block
     for (size_t N : {1u, 2u, 7u, 1024u, 1025u}) {
-        const size_t c = rs_chunk_elems(2048, 4, N);
+        const size_t c = host_chunk_elems(2048, 4, N);
         size_t seen = 0;
         for (size_t off = 0; off < N; off += c) seen += N - off < c ? N - off : c;
         CHECK(seen == N);
@@ -77,20 +83,28 @@ static int fold(int P, int nreduce, bool overlap)
         int32_t *acc = (int32_t *) malloc(b.bytes ? b.bytes : 1);
         int32_t *peer = P > 1 ? (int32_t *) malloc(b.bytes ? b.bytes : 1) : nullptr;
         int gets = 0, betweens = 0;
-        const bool ok = osgpu::rt::rs_host_fold(
-            b, heap[m], acc, peer, order.data(), P, (size_t) nreduce,
+        bool sized = true;
+        // the table of one entry: block m of my source, pre-offset
+        void *accs[1] = {acc};
+        const void *mine[1] = {(const char *) heap[m] + b.offset};
+        const size_t bytes[1] = {b.bytes}, nelems[1] = {(size_t) nreduce};
+        const bool ok = osgpu::rt::many_host_fold(
+            1, accs, mine, bytes, nelems, peer, order.data(), P,
             [&](void *dst, const void *src, size_t n, int pe) {
                 // the runtime's getmem: `src` is MY address of a symmetric object
                 const size_t off = (const char *) src - (const char *) heap[m];
+                sized = sized && n == b.bytes && off == b.offset;
                 memcpy(dst, (const char *) heap[pe] + off, n);
                 gets++;
             },
-            [&](void *a, const void *in, size_t n) {
+            [&](void *a, const void *in, size_t n, int entry) {
+                sized = sized && entry == 0 && n == (size_t) nreduce;
                 for (size_t i = 0; i < n; i++) ((int32_t *) a)[i] += ((const int32_t *) in)[i];
                 return true;
             },
             [&] { betweens++; });
-        CHECK(ok && gets == P - 1 && betweens == 1);
+        // one getmem of exactly the block per peer; an empty block is skipped
+        CHECK(ok && sized && gets == (b.bytes ? P - 1 : 0) && betweens == 1);
         for (int k = 0; k < nreduce; k++) {
             int32_t want = 0;
             for (int p = 0; p < P; p++) want += (int32_t) (1000 * p + (size_t) m * nreduce + k);

@@ -79,7 +79,7 @@ static int chunks()
     for (size_t n : ns)
         for (size_t cb : cbs)
             for (size_t e : elems) {
-                const size_t chunk = scan_chunk_elems(cb, e, n);
+                const size_t chunk = host_chunk_elems(cb, e, n);
                 CHECK(chunk >= 1 && chunk % 2 == 0 && chunk <= n + 1);
                 std::vector<unsigned char> hit(n, 0);  // allocated to the element
                 size_t next = 0, calls = 0;
