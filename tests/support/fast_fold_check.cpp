@@ -1,6 +1,6 @@
 // fast_fold_check.cpp -- TEST INFRASTRUCTURE: the premise of the branch-free
 // folds (csrc/elem_ops.hpp Fast<T, OP>) on the host, with its own main, built
-// plain and with ASan + UBSan by fast_fold_build.py.
+// plain and with ASan + UBSan by host_check_build.py.
 // usage: fast_fold_check premise      every floating (type, op) with kChecked,
 //                                     all triples of an alphabet
 //        fast_fold_check route FILE   the kernels' route (the fast fold of a

@@ -2,7 +2,7 @@
 // setup (csrc/psync_board.hpp, fd_channel.cpp, heap_host.hpp) driven on the
 // CPU.  Threads stand in for PEs behind a barrier-and-getmem stub.
 //   heap_host_check <case>     exit 0 and "ok", or 1 and what failed
-// Built by heap_host_build.py, plain and with ASan + UBSan; run by
+// Built by host_check_build.py, plain and with ASan + UBSan; run by
 // tests/test_heap_host.py.
 #include <dirent.h>
 #include <sys/mman.h>

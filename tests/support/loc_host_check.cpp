@@ -1,7 +1,7 @@
 // loc_host_check.cpp -- TEST INFRASTRUCTURE: the HIP-free arithmetic of
 // osgpu_reduce_loc (csrc/loc_host.hpp) and its step (csrc/elem_ops.hpp LocStep
 // compiled for the host) with their own main, built plain and with ASan +
-// UBSan by loc_host_build.py.
+// UBSan by host_check_build.py.
 // usage: loc_host_check arith        the pair table, byte counts, overlap rule,
 //                                    vector split, GETMEM chunk, input chunks
 //        loc_host_check fold FILE    the cases Python wrote to FILE, folded by

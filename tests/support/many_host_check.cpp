@@ -1,6 +1,6 @@
 // many_host_check.cpp -- TEST INFRASTRUCTURE: the HIP-free logic of the
 // batched reduce-to-all (csrc/many_host.hpp) with its own main, built plain
-// and with ASan + UBSan (tests/support/many_host_build.py): the routes, the
+// and with ASan + UBSan (tests/support/host_check_build.py): the routes, the
 // packing plan, the overlap check of the table and the host fold's loop.
 // Every array of the host-fold cases is a malloc of EXACTLY its bytes.
 // Prints "ok".

@@ -1,6 +1,6 @@
 // rscatter_host_check.cpp -- TEST INFRASTRUCTURE: the HIP-free arithmetic of
 // osgpu_reduce_scatter's host paths with its own main, built plain and with
-// ASan + UBSan (tests/support/rscatter_host_build.py): the block's bytes
+// ASan + UBSan (tests/support/host_check_build.py): the block's bytes
 // (csrc/rscatter_host.hpp), and the two helpers the call shares with the
 // other collectives AS IT USES THEM -- GETMEM's chunk over the block
 // (scan_host.hpp host_chunk_elems) and the host fold over a table of one

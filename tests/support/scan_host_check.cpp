@@ -1,6 +1,6 @@
 // scan_host_check.cpp -- TEST INFRASTRUCTURE: the HIP-free arithmetic of
 // osgpu_scan (csrc/scan_host.hpp) with its own main, built plain and with
-// ASan + UBSan by scan_host_build.py.
+// ASan + UBSan by host_check_build.py.
 // usage: scan_host_check CASE   (prefix | bytes | chunks | identity); prints
 // "ok" and exits 0, or the first failed check and 1.
 #include <limits.h>

@@ -36,6 +36,7 @@ import oracle as O
 import osgpu
 from support import guarded as G
 from support import half_ref as R
+from support.gpu_doors import small_launches, stream, torch_cuda  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -48,40 +49,6 @@ NPOOL = 17                # inputs per type: the largest K
 ARENA_BYTES = 48 << 20    # a batch is flushed past this
 
 TYPES = [t for t in O.TYPES if LD_ON_GPU or t != "longdouble"] + list(R.TYPES)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-@pytest.fixture
-def small_launches(monkeypatch):
-    """At most 2048 threads per launch (the osgpu_test_max_launch_threads
-    hook, as tests/test_gpu_parity.py small_launches): the multi-launch path
-    of calls of 2^31+ threads, at small sizes; restored after."""
-    monkeypatch.setenv("OSGPU_TEST_HOOKS", "1")
-    L = osgpu.load()
-    L.osgpu_test_max_launch_threads.argtypes = [ctypes.c_longlong]
-    assert L.osgpu_test_max_launch_threads(2048) == 0, L.osgpu_last_error()
-    yield
-    assert L.osgpu_test_max_launch_threads(0) == 0
-
-
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (a NULL stream
-    means "the calling thread's stream" to the launchers, which is not
-    ordered after torch's uploads; tests/test_gpu_parity.py _stream)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 # ------------------------------------------------------------ types and sizes
@@ -252,9 +219,9 @@ class Batch:
     def flush(self):
         if self.cases:
             self.arena.upload(self.torch)
-            stream = _stream(self.torch)
+            sp = stream(self.torch)
             for launch, _ in self.cases:
-                launch(stream)
+                launch(sp)
             self.torch.cuda.synchronize()
             self.arena.download()
             for _, checks in self.cases:
@@ -311,6 +278,7 @@ def test_combine_run_edges_multi_launch(torch_cuda, small_launches, t, phase_in,
     (vector form), every boundary +-1 vector.  sum, and at K = 2 and 8 a
     second op (max; complex: prod).  (complexd's non-zero phase, 8, is the
     element-granular kernel's.)"""
+    small_launches(2048)
     ns = sizes(t, SET_B, phase_in, phase_out)
     b = Batch(torch_cuda, t, phase_in, max(KS_B), max(ns))
     other = "max" if "max" in ops_of(t) else "prod"
@@ -376,6 +344,7 @@ def test_team_tile_edges(torch_cuda, t, op, P, remote):
 def test_team_run_edges_multi_launch(torch_cuda, small_launches, t, op, P):
     """The team kernels over set B under the 2048-thread hook (runs are
     whole multiples of the combine's), phase 0 and one non-zero phase."""
+    small_launches(2048)
     for phase_in, phase_out in (team_phases(t)[0], team_phases(t)[1]):
         ns = sizes(t, SET_B, phase_in, phase_out)
         b = Batch(torch_cuda, t, phase_in, P, max(ns))

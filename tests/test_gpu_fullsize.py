@@ -22,18 +22,11 @@ import ctypes
 import pytest
 
 import osgpu
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 P = 8
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def _team(torch, t, op, srcs, dsts, n):

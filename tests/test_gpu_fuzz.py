@@ -22,17 +22,10 @@ import pytest
 import oracle as O
 import osgpu
 from support import guarded
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 
 HEAP = 8 << 20
 NCASE = int(os.environ.get("OSGPU_FUZZ_CASES", "800"))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 _TEAMS = {}

@@ -10,28 +10,11 @@ import pytest
 
 import osgpu
 from support import half_ref as R
+from support.gpu_doors import stream, torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 PAIRS = [(t, o) for t in R.TYPES for o in R.OPS]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
-
-
-def _stream(torch):
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 def _dev(torch, arr, pad=64):
@@ -82,14 +65,14 @@ def test_exhaustive_device_arithmetic(torch_cuda, t, op):
     da, db = _dev(torch, a), _dev(torch, b)
     out = torch.zeros(a.size * 2 + 128, dtype=torch.uint8, device="cuda:0")
     osgpu.combine(t, op, out.data_ptr() + 64, [da.data_ptr() + 64, db.data_ptr() + 64], a.size,
-                  _stream(torch))
+                  stream(torch))
     msg = _mismatch(_host(torch, out, 64, a.size), want)
     assert not msg, f"vector form {t} {op}: {msg}"
     out.zero_()
     # b at another 16-byte phase: the element-granular kernel
     db2 = _dev(torch, b, pad=66)
     osgpu.combine(t, op, out.data_ptr() + 64, [da.data_ptr() + 64, db2.data_ptr() + 66], a.size,
-                  _stream(torch))
+                  stream(torch))
     msg = _mismatch(_host(torch, out, 64, a.size), want)
     assert not msg, f"element-granular form {t} {op}: {msg}"
 
@@ -128,7 +111,7 @@ def test_combine_shapes(torch_cuda, t, K):
                 want = R.fold(t, op, list(range(K)), [s[o2:o2 + m] for s in src])
                 out.fill_(0xA5)
                 osgpu.combine(t, op, out.data_ptr() + 64 + off,
-                              [d.data_ptr() + 64 + off for d in dev], m, _stream(torch))
+                              [d.data_ptr() + 64 + off for d in dev], m, stream(torch))
                 got = _host(torch, out, 64 + off, m)
                 assert not _mismatch(got, want), (t, op, K, n, off, _mismatch(got, want))
                 raw = out.cpu().numpy()
@@ -137,14 +120,14 @@ def test_combine_shapes(torch_cuda, t, K):
                 want = R.fold(t, op, list(range(K)), [s[:n] for s in src])
                 out.fill_(0)
                 ptrs = [d.data_ptr() + 64 for d in dev[:-1]] + [dev_odd.data_ptr() + 72]
-                osgpu.combine(t, op, out.data_ptr() + 64, ptrs, n, _stream(torch))
+                osgpu.combine(t, op, out.data_ptr() + 64, ptrs, n, stream(torch))
                 got = _host(torch, out, 64, n)
                 assert not _mismatch(got, want), (t, op, K, n, "phase", _mismatch(got, want))
     # target aliasing source 0
     n = _combine_ns(K)[-1]
     d0 = _dev(torch, src[0])
     osgpu.combine(t, "sum", d0.data_ptr() + 64, [d0.data_ptr() + 64] + [d.data_ptr() + 64 for d in dev[1:]],
-                  n, _stream(torch))
+                  n, stream(torch))
     want = R.fold(t, "sum", list(range(K)), [s[:n] for s in src])
     got = _host(torch, d0, 64, n)
     assert not _mismatch(got, want), (t, K, "alias", _mismatch(got, want))
@@ -174,7 +157,7 @@ def test_nan_tile_recompute(torch_cuda, t, op):
     da, db = _dev(torch, a), _dev(torch, b)
     out = torch.zeros(n * 2 + 128, dtype=torch.uint8, device="cuda:0")
     osgpu.combine(t, op, out.data_ptr() + 64, [da.data_ptr() + 64, db.data_ptr() + 64], n,
-                  _stream(torch))
+                  stream(torch))
     got = _host(torch, out, 64, n)
     assert not _mismatch(got, want), _mismatch(got, want)
     keep = np.ones(n, bool)
@@ -211,7 +194,7 @@ def test_team_kernel(torch_cuda, t, P):
             ins = [_dev(torch, s, pad=74) for s in src]
             outs = [torch.zeros(n * 2 + 160, dtype=torch.uint8, device="cuda:0") for _ in range(P)]
             osgpu.team_combine(t, op, [o.data_ptr() + 74 for o in outs],
-                               [i.data_ptr() + 74 for i in ins], n, _stream(torch), remote=remote)
+                               [i.data_ptr() + 74 for i in ins], n, stream(torch), remote=remote)
             for q in range(P):
                 got = _host(torch, outs[q], 74, n)
                 assert not _mismatch(got, want[q]), (t, op, P, remote, q, _mismatch(got, want[q]))

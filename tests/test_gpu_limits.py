@@ -14,16 +14,9 @@ import ctypes
 import pytest
 
 import osgpu
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def _team(P, heap_bytes):

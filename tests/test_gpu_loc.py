@@ -26,42 +26,20 @@ wins" or "last holder wins" kernel from a right one).
 """
 import ctypes
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import osgpu
+from support import gpu_doors as D
 from support import guarded as G
 from support import loc_cases as C
+from support.gpu_doors import small_launches, torch_cuda  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
 _POOL = {}
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (NULL means the
-    calling thread's stream to the launchers, which is not ordered after
-    torch's uploads)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 def nmax(t):
@@ -94,52 +72,36 @@ def lengths(t):
     return sorted({0, 1, g - 1, g, g + 1, T - 1, T, T + 1, 2 * T + g + 1})
 
 
-class Batch:
-    """Cases of one (type, op) in one arena: one upload, the launches, one
-    synchronize, one download."""
+class Batch(D.LauncherBatch):
+    """Cases of one (type, op): a case's targets are its ndst value targets,
+    then its ndst index targets; its sources the values, then the indices."""
 
     def __init__(self, t, op):
-        self.t, self.op, self.s = t, op, C.esize(t)
+        super().__init__(t)
+        self.op = op
         self.vals, self.locs, _ = pool(t, op)
-        self.arena = G.Arena()
-        self.cases = []
 
     def add(self, P, ndst, n, what, vsp=None, lsp=None, vdp=None, ldp=None, member_locs=None):
         """vsp / lsp / vdp / ldp: the 16-byte phases of the value sources, index
         sources, value targets and index targets (default 0)."""
         ph = lambda a, k: 0 if a is None else a[k]
         vs = [self.arena.add(n * self.s, ph(vsp, p), self.vals[p][:n]) for p in range(P)]
-        ls = None if member_locs is not None else [
+        ls = [] if member_locs is not None else [
             self.arena.add(n * 4, ph(lsp, p), self.locs[p][:n]) for p in range(P)]
         vd = [self.arena.add(n * self.s, ph(vdp, q)) for q in range(ndst)]
         ld = [self.arena.add(n * 4, ph(ldp, q)) for q in range(ndst)]
-        self.cases.append((P, n, vs, ls, vd, ld, member_locs, what))
+        self.case(vs + ls, vd + ld, what, op=self.op, P=P, ndst=ndst, n=n, member_locs=member_locs)
 
-    def launch(self, torch):
-        self.arena.upload(torch)
-        sp = _stream(torch)
-        for P, n, vs, ls, vd, ld, ml, _ in self.cases:
-            osgpu.team_loc(self.t, self.op, [g.ptr for g in vd], [g.ptr for g in ld],
-                           [g.ptr for g in vs], None if ls is None else [g.ptr for g in ls], n,
-                           member_locs=ml, stream=sp)
-        torch.cuda.synchronize()
-        self.arena.download()
-        return self
+    def call(self, c, sp):
+        osgpu.team_loc(self.t, self.op, D.ptrs(c.dsts[:c.ndst]), D.ptrs(c.dsts[c.ndst:]),
+                       D.ptrs(c.srcs[:c.P]), D.ptrs(c.srcs[c.P:]) or None, c.n,
+                       member_locs=c.member_locs, stream=sp)
 
-    def check(self):
-        for P, n, vs, ls, vd, ld, ml, what in self.cases:
-            what = f"{self.t} {self.op} P={P} ndst={len(vd)} n={n} {what}"
-            wv, wi = want(self.t, self.op, P, n, ml)
-            for q, (gv, gl) in enumerate(zip(vd, ld)):
-                bad = C.same_bits(self.t, gv.data().view(C.dtype(self.t)), wv)
-                assert bad is None, f"{what}: target {q}, value {bad} differs from the oracle"
-                got = gl.data().view(np.int32)
-                assert np.array_equal(got, wi), \
-                    f"{what}: target {q}, index {int(np.flatnonzero(got != wi)[0])} differs"
-                gv.assert_guards(f"{what} value target {q}")
-                gl.assert_guards(f"{what} index target {q}")
-            for p, g in enumerate(vs + (ls or [])):
-                g.assert_unchanged(f"{what} source {p}")
+    def out_type(self, c, q):
+        return self.t if q < c.ndst else "int"
+
+    def want(self, c, q):
+        return want(self.t, self.op, c.P, c.n, c.member_locs)[q >= c.ndst]
 
 
 # ------------------------------------------------------------ 1. lengths
@@ -219,7 +181,7 @@ def test_values_are_the_uniform_reduce(torch_cuda, t, op):
     ls = [a.add(n * 4, 0, locs[p][:n]) for p in range(P)]
     vd, ld, ud = ([a.add(n * k) for _ in range(P)] for k in (s, 4, s))
     a.upload(torch)
-    sp = _stream(torch)
+    sp = D.stream(torch)
     osgpu.team_loc(t, op, [g.ptr for g in vd], [g.ptr for g in ld], [g.ptr for g in vs],
                    [g.ptr for g in ls], n, stream=sp)
     osgpu.team_uniform(t, op, [g.ptr for g in ud], [g.ptr for g in vs], n, stream=sp)
@@ -233,19 +195,6 @@ def test_values_are_the_uniform_reduce(torch_cuda, t, op):
 
 
 # --------------------------------------------------------- 5. multi-launch
-@pytest.fixture
-def small_launches(monkeypatch):
-    """osgpu_test_max_launch_threads: the multi-launch path at small sizes."""
-    monkeypatch.setenv("OSGPU_TEST_HOOKS", "1")
-    L = osgpu.load()
-    L.osgpu_test_max_launch_threads.argtypes = [ctypes.c_longlong]
-
-    def set_limit(n):
-        assert L.osgpu_test_max_launch_threads(n) == 0, L.osgpu_last_error()
-    yield set_limit
-    assert L.osgpu_test_max_launch_threads(0) == 0
-
-
 @pytest.mark.parametrize("t,op", [("half", "max"), ("int", "min"), ("double", "max")],
                          ids=lambda x: x)
 def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
@@ -263,7 +212,7 @@ def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
                   vdp=[s] * ndst, ldp=[4] * ndst)
         b.add(3, 3, 3 * T + 1, f"limit {limit} member_locs", member_locs=[1, 3, 5])
         b.launch(torch_cuda).check()
-        res.append([d.data().copy() for c in b.cases for d in c[4] + c[5]])
+        res.append([d.data().copy() for c in b.cases for d in c.dsts])
     for one, many in zip(*res):
         assert np.array_equal(one, many)
 
@@ -368,17 +317,13 @@ def test_collective_target_sub_view(torch_cuda):
 
 
 def test_collective_pull_forms(torch_cuda):
-    L = osgpu.load()
     for t, op, n in (("float", "max", 1001), ("short", "min", 2 * C.tile_elems("short") + 3),
                      ("long", "max", 777)):
         ref = _collective(t, op, 3, n, 0xE0)
         nref = _collective(t, op, 3, n, 0xE0, null=True)
-        try:
-            assert L.osgpu_set_path(osgpu.PATH_PULL) == 0
+        with D.forced_path(osgpu.PATH_PULL):
             _collective(t, op, 3, n, 0xE0, path="pull", ref=ref)
             _collective(t, op, 3, n, 0xE0, path="pull", null=True, ref=nref)
-        finally:
-            L.osgpu_set_path(osgpu.PATH_AUTO)
         _collective(t, op, 3, n, 0xE0, path="pull", in_place=True, ref=ref)
         _collective(t, op, 3, n, 0xE0, path="pull", outside=True, ref=ref)
         _collective(t, op, 3, n, 0xE0, path="pull", outside=True, null=True, ref=nref)
@@ -400,24 +345,16 @@ def test_collective_host_heaps(torch_cuda, path):
     """Host fold and GETMEM (forced by the fold limit / osgpu_set_host_path; a
     forced STAGED takes GETMEM), the chunk below the array size; a strided
     set, in place, one member, 9 members, both index forms."""
-    L = osgpu.load()
     cases = [("double", "max", 3, 0, 0, 3, 1001, False, False), ("short", "min", 2, 0, 0, 2, 5, False, True),
              ("float", "min", 8, 1, 1, 3, 700, False, True), ("int", "max", 3, 0, 0, 3, 1001, True, False),
              ("half", "max", 3, 0, 0, 3, 1501, False, False), ("long", "min", 1, 0, 0, 1, 9, False, False),
              ("bfloat16", "min", 9, 0, 0, 9, 333, False, False), ("float", "max", 9, 0, 0, 9, 333, False, True),
              ("float", "max", 8, 0, 0, 8, 1001, False, False)]
-    ran = "host_fold" if path == "host_fold" else "getmem"
-    try:
+    with D.host_heaps(path) as (force, team, ran):
         for t, op, npes, start, log, size, n, ov, null in cases:
-            if path != "host_fold":
-                assert L.osgpu_set_host_path(osgpu.HOST_PATHS[path]) == 0
-                assert L.osgpu_set_host_chunk_bytes(2048) == 0
+            force()
             _collective(t, op, npes, n, 0xD0 + size, start, log, size, path=ran, null=null,
-                        in_place=ov, device=False, host_fold=(path == "host_fold"))
-    finally:
-        L.osgpu_set_host_path(-1)
-        L.osgpu_set_host_chunk_bytes(-1)
-        L.osgpu_set_host_fold_max_bytes(-1)
+                        in_place=ov, **team)
 
 
 # ------------------------------------------------------------ 9. two processes
@@ -426,26 +363,7 @@ def test_two_processes_one_gpu(torch_cuda, tmp_path):
     writes a peer's two targets through a mapping of another process's memory
     (tests/support/loc_mp_worker.py starts nothing itself; the ranks are fresh
     child processes of this test)."""
-    worker = os.path.join(ROOT, "tests", "support", "loc_mp_worker.py")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path)],
-                              env=dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
-                                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                                       PYTHONUNBUFFERED="1"),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for r in range(2)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=150)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and "LOC_MP_OK" in o, f"rank {r}:\n{o[-3000:]}"
+    D.run_ranks("loc_mp_worker.py", tmp_path, "LOC_MP_OK")
 
 
 # -------------------------------------------------------------------- 10. fuzz
@@ -461,8 +379,6 @@ def test_fuzz_30_calls(torch_cuda):
         overlap = bool(rng.integers(4) == 0)
         team = 2 <= P <= 8 and not overlap
         what = f"seed {seed} call {i}: {t} {op} P={P} n={n} shift={shift} null={null} overlap={overlap}"
-        try:
+        with D.named(what):
             _collective(t, op, P, n, seed + i, shift=0 if overlap else shift, in_place=overlap,
                         null=null, path="team" if team else "pull")
-        except AssertionError as e:
-            raise AssertionError(f"{what}: {e}") from None

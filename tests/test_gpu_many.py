@@ -33,7 +33,6 @@
 """
 import ctypes
 import os
-import socket
 import subprocess
 import sys
 
@@ -41,9 +40,11 @@ import numpy as np
 import pytest
 
 import osgpu
+from support import gpu_doors as D
 from support import guarded as G
 from support import many_cases as M
 from support import rscatter_cases as C
+from support.gpu_doors import small_launches, torch_cuda  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,83 +55,53 @@ ALL_PAIRS = ([(t, o) for t in osgpu.TYPES for o in osgpu.OPS if osgpu.has_op(t, 
 assert len(ALL_PAIRS) == 52
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (NULL means the
-    calling thread's stream to the launchers, which is not ordered after
-    torch's uploads)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
-
-
 def lengths(t):
     W = 16 // C.esize(t)
     return [1, max(W - 1, 1), W, W + 1, V * W - 1, V * W, V * W + 1, 2 * V * W + W - 1]
 
 
 # ------------------------------------------------------------ 1. raw launcher
-class Tables:
-    """Calls of osgpu_combine_many for one (type, op) in one arena: one
-    upload, the launches, one synchronize, one download.  Inputs: kmax arrays
-    of nmax elements, one copy of each per 16-byte phase in use."""
+class Tables(D.LauncherBatch):
+    """Calls of osgpu_combine_many for one (type, op): a case is one call, its
+    targets the entries'.  Inputs: kmax arrays of nmax elements, one copy of
+    each per 16-byte phase in use, shared by every call (so a case lists no
+    sources of its own: check() looks at the shared ones once)."""
 
     def __init__(self, t, op, kmax, nmax, seed):
-        self.t, self.op, self.s = t, op, C.esize(t)
-        self.nmax = nmax
+        super().__init__(t)
+        self.op, self.nmax = op, nmax
         self.pool = C.inputs(t, op, kmax, nmax, seed)
-        self.want = {}      # K -> fold of pool[:K] at nmax
-        self.arena = G.Arena()
+        self.fold = {}      # K -> fold of pool[:K] at nmax
         self.src = {}       # (phase, k) -> Guarded
-        self.calls = []     # (K, [(n, target, [sources], what)])
 
     def source(self, phase, k):
         if (phase, k) not in self.src:
             self.src[(phase, k)] = self.arena.add(self.nmax * self.s, phase, self.pool[k])
         return self.src[(phase, k)]
 
-    def call(self, K, entries, what):
+    def call_of(self, K, entries, what):
         """entries: (n, target phase, [source phases]) each."""
-        rows = []
-        for n, tp, sps in entries:
-            rows.append((n, self.arena.add(n * self.s, tp), [self.source(sps[k], k) for k in range(K)]))
-        self.calls.append((K, rows, what))
+        rows = [(n, self.arena.add(n * self.s, tp), [self.source(sps[k], k) for k in range(K)])
+                for n, tp, sps in entries]
+        self.case([], [r[1] for r in rows], what, op=self.op, K=K, lens=[r[0] for r in rows],
+                  ins=[r[2] for r in rows])
 
-    def launch(self, torch):
-        self.arena.upload(torch)
-        sp = _stream(torch)
-        for K, rows, _ in self.calls:
-            osgpu.combine_many(self.t, self.op, [r[1].ptr for r in rows],
-                               [[g.ptr for g in r[2]] for r in rows], [r[0] for r in rows], stream=sp)
-        torch.cuda.synchronize()
-        self.arena.download()
-        return self
+    def call(self, c, sp):
+        osgpu.combine_many(self.t, self.op, D.ptrs(c.dsts), [D.ptrs(g) for g in c.ins], c.lens,
+                           stream=sp)
+
+    def want(self, c, q):
+        if not c.lens[q]:
+            return self.pool[0][:0]
+        if c.K not in self.fold:
+            self.fold[c.K] = C.fold_left(self.t, self.op, self.pool[:c.K])
+        return self.fold[c.K][:c.lens[q]]
+
+    def describe(self, c):
+        return f"{self.t} {self.op} K={c.K} {c.what}, {len(c.lens)} entries of n={c.lens}"
 
     def check(self):
-        for K, rows, what in self.calls:
-            for i, (n, out, _) in enumerate(rows):
-                w = f"{self.t} {self.op} K={K} {what} entry {i} of {len(rows)} n={n}"
-                out.assert_guards(w + " target")
-                if n == 0:
-                    continue
-                if K not in self.want:
-                    self.want[K] = C.fold_left(self.t, self.op, self.pool[:K])
-                got = out.data().view(C.dtype(self.t))
-                if self.t == "longdouble":
-                    assert not out.data().reshape(-1, 16)[:, 10:].any(), f"{w}: long double padding"
-                bad = C.same_bits(self.t, got, self.want[K][:n])
-                assert bad is None, f"{w}: element {bad} differs from the oracle's fold"
+        super().check()
         for (phase, k), g in self.src.items():
             g.assert_unchanged(f"{self.t} {self.op} input {k} at phase {phase}")
         return self
@@ -157,16 +128,16 @@ def test_launcher_batches(torch_cuda, t, op):
     b = Tables(t, op, 9, max(lengths(t)), 0x3A47 + s)
     for K in (2, 3, 8):
         for count in (1, 2, 15, 16, 17, 33):
-            b.call(K, _mixed(t, count, K, salt=K + count), f"batch of {count}")
+            b.call_of(K, _mixed(t, count, K, salt=K + count), f"batch of {count}")
     # the fall-backs among batch entries
     n = V * W + 1
     off = s if W > 1 else 8         # a target one element off its sources' phase (complexd: 8 bytes)
     fb = [(n, 0, [0] * 3), (n, off, [0] * 3), (W + 1, 0, [0] * 3)]
     if s > 1 and t != "complexd":   # a pointer off its element alignment
         fb += [(n, 0, [0, s // 2, 0]), (W + 1, s // 2, [0] * 3)]
-    b.call(3, fb + [(max(lengths(t)), 0, [0] * 3)], "phase fall-backs")
-    b.call(1, _mixed(t, 3, 1), "one input")
-    b.call(9, _mixed(t, 3, 9) + [(n, off, [0] * 9)], "nine inputs")
+    b.call_of(3, fb + [(max(lengths(t)), 0, [0] * 3)], "phase fall-backs")
+    b.call_of(1, _mixed(t, 3, 1), "one input")
+    b.call_of(9, _mixed(t, 3, 9) + [(n, off, [0] * 9)], "nine inputs")
     b.launch(torch_cuda).check()
 
 
@@ -176,46 +147,34 @@ def test_launcher_batches(torch_cuda, t, op):
 def test_launcher_16_byte_elements(torch_cuda, t, op, phase):
     b = Tables(t, op, 9, 2 * V + 1, 0x16B)
     for K in (1, 2, 3, 9):
-        b.call(K, [(n, phase, [0] * K) for n in (1, V, 0, 2 * V + 1, V + 1)], f"target phase {phase}")
-    b.call(2, [((i * 37) % (2 * V) + 1, phase, [0, 0]) for i in range(17)], "17 entries")
+        b.call_of(K, [(n, phase, [0] * K) for n in (1, V, 0, 2 * V + 1, V + 1)], f"target phase {phase}")
+    b.call_of(2, [((i * 37) % (2 * V) + 1, phase, [0, 0]) for i in range(17)], "17 entries")
     b.launch(torch_cuda).check()
 
 
 # ------------------------------------------------------------------ 2. routes
-@pytest.fixture
-def hooks(monkeypatch):
-    monkeypatch.setenv("OSGPU_TEST_HOOKS", "1")
-    L = osgpu.load()
-    L.osgpu_test_max_launch_threads.argtypes = [ctypes.c_longlong]
-    L.osgpu_test_many_routes.argtypes = [ctypes.POINTER(ctypes.c_ulonglong * 7)]
-
-    def set_limit(n):
-        assert L.osgpu_test_max_launch_threads(n) == 0, L.osgpu_last_error()
-    yield set_limit
-    assert L.osgpu_test_max_launch_threads(0) == 0
-
-
 def _routes():
     """osgpu_test_many_routes: [segments on the batch kernel, entries on the
     shifted combine, on the long double kernel, on the chunks of 8, on the
     one-input copy, launches of the batch kernel, continuations]."""
     c = (ctypes.c_ulonglong * 7)()
     L = osgpu.load()
+    L.osgpu_test_many_routes.argtypes = [ctypes.POINTER(ctypes.c_ulonglong * 7)]
     assert L.osgpu_test_many_routes(ctypes.byref(c)) == 0, L.osgpu_last_error()
     return np.array(list(c), dtype=np.int64)
 
 
-def test_routes(torch_cuda, hooks):
+def test_routes(torch_cuda, small_launches):
     t, op, s, W = "float", "prod", 4, 4
 
     def delta(K, entries, t=t, op=op):
         b = Tables(t, op, K, max(e[0] for e in entries), 0xA0)
-        b.call(K, entries, "route")
+        b.call_of(K, entries, "route")
         before = _routes()
         b.launch(torch_cuda).check()
-        return list(_routes() - before), [r[1].data().copy() for r in b.calls[0][1]]
+        return list(_routes() - before), [g.data().copy() for g in b.cases[0].dsts]
 
-    hooks(0)
+    small_launches(0)
     n = V * W + 1
     same = [(n + i, (i % W) * s, [(i % W) * s] * 2) for i in range(17)]
     assert delta(2, same)[0] == [17, 0, 0, 0, 0, 2, 0], "17 entries: 16 segments and 1"
@@ -232,7 +191,7 @@ def test_routes(torch_cuda, hooks):
     five = [(5 * V * W, 0, [0, 0])]
     one, bits_one = delta(2, five)
     assert one == [1, 0, 0, 0, 0, 1, 0]
-    hooks(3 * 128)
+    small_launches(3 * 128)
     try:
         split, bits_split = delta(2, five)
         assert split == [2, 0, 0, 0, 0, 2, 1], "tiles [0, 3) and the continuation [3, 5)"
@@ -241,11 +200,11 @@ def test_routes(torch_cuda, hooks):
         edgy = [(7, s, [s, s]), (5 * V * W - 2, 2 * s, [2 * s] * 2), (9, 0, [0, 0])]
         assert delta(2, edgy)[0] == [4, 0, 0, 0, 0, 3, 1]
     finally:
-        hooks(0)
+        small_launches(0)
 
 
 # ---------------------------------------------------- 3. collective, PE threads
-def _collective(torch, t, op, npes, lens, seed, PE_start=0, log=0, PE_size=None, inplace=(),
+def _collective(t, op, npes, lens, seed, PE_start=0, log=0, PE_size=None, inplace=(),
                 odd=None, sodd=None, device=True, host_fold=False, path="pull", setup=None):
     """One osgpu_reduce_many on a fresh team, checked against the oracle
     entry by entry, then against the same table as single calls."""
@@ -315,44 +274,33 @@ def _table(t, count):
 def test_collective_device_heaps(torch_cuda, P, count):
     for t, op in COLL_PAIRS:
         lens, inplace, odd = _table(t, count)
-        _collective(torch_cuda, t, op, P, lens, 0xD0 + P + count, inplace=inplace, odd=odd)
+        _collective(t, op, P, lens, 0xD0 + P + count, inplace=inplace, odd=odd)
 
 
 def test_collective_strided_active_set(torch_cuda):
     lens, inplace, odd = _table("double", 17)
-    _collective(torch_cuda, "double", "sum", 8, lens, 5, PE_start=1, log=1, PE_size=3,
+    _collective("double", "sum", 8, lens, 5, PE_start=1, log=1, PE_size=3,
                 inplace=inplace, odd=odd)
-    _collective(torch_cuda, "int", "sum", 6, [259, 0, 3], 6, PE_start=0, log=1, PE_size=3)
+    _collective("int", "sum", 6, [259, 0, 3], 6, PE_start=0, log=1, PE_size=3)
 
 
 def test_collective_edges(torch_cuda):
     """All entries empty, count == 0, a single member (copies; long double
     padding zeroed), sources at a phase their targets share."""
-    _collective(torch_cuda, "int", "sum", 2, [0, 0, -3], 1)
-    _collective(torch_cuda, "int", "sum", 2, [], 1)
-    _collective(torch_cuda, "longdouble", "sum", 1, [9, 0, 257], 2, inplace=(2,))
-    _collective(torch_cuda, "short", "min", 4, [1001, 33], 3, PE_start=2, PE_size=1)
-    _collective(torch_cuda, "float", "max", 3, [1001, 2051, 5], 4, odd={0: 1, 1: 3}, sodd={0: 1, 1: 3})
+    _collective("int", "sum", 2, [0, 0, -3], 1)
+    _collective("int", "sum", 2, [], 1)
+    _collective("longdouble", "sum", 1, [9, 0, 257], 2, inplace=(2,))
+    _collective("short", "min", 4, [1001, 33], 3, PE_start=2, PE_size=1)
+    _collective("float", "max", 3, [1001, 2051, 5], 4, odd={0: 1, 1: 3}, sodd={0: 1, 1: 3})
 
 
 # ------------------------------------------------------ 4. host heaps (need a GPU)
 @pytest.mark.parametrize("P", [2, 3])
 @pytest.mark.parametrize("path", ["host_fold", "getmem"])
 def test_collective_host_heaps(torch_cuda, path, P):
-    L = osgpu.load()
-
-    def force():
-        assert L.osgpu_set_host_path(osgpu.HOST_GETMEM) == 0
-        assert L.osgpu_set_host_chunk_bytes(2048) == 0
-    try:
+    with D.host_heaps(path) as (force, team, ran):
         for t, op in (("double", "sum"), ("bfloat16", "prod"), ("longdouble", "sum")):
-            _collective(torch_cuda, t, op, P, [1001, 0, 300], 31 + P, inplace=(2,), device=False,
-                        host_fold=(path == "host_fold"), path=path,
-                        setup=force if path == "getmem" else None)
-    finally:
-        L.osgpu_set_host_path(-1)
-        L.osgpu_set_host_chunk_bytes(-1)
-        L.osgpu_set_host_fold_max_bytes(-1)
+            _collective(t, op, P, [1001, 0, 300], 31 + P, inplace=(2,), path=ran, setup=force, **team)
 
 
 # ------------------------------------------------------------ 5. two processes
@@ -360,26 +308,7 @@ def test_two_processes_one_gpu(torch_cuda, tmp_path):
     """2 ranks, one process each, heaps made by osgpu_heap_create: the pull
     path over a peer mapping (tests/support/many_mp_worker.py), each worker
     under its own time limit."""
-    worker = os.path.join(ROOT, "tests", "support", "many_mp_worker.py")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = [subprocess.Popen(["timeout", "-k", "10", "150", sys.executable, worker, str(tmp_path)],
-                              env=dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
-                                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                                       PYTHONUNBUFFERED="1"),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for r in range(2)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=180)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and "MANY_MP_OK" in o, f"rank {r} (status {p.returncode}):\n{o[-3000:]}"
+    D.run_ranks("many_mp_worker.py", tmp_path, "MANY_MP_OK")
 
 
 # ---------------------------------------------------------- 6. fatal contract
@@ -438,7 +367,5 @@ def test_fuzz_30_calls(torch_cuda):
         sodd = {j: odd[j] if rng.integers(3) else int(rng.integers(0, max(W, 2))) for j in range(count)}
         inplace = tuple(j for j in range(count) if rng.integers(5) == 0)
         what = f"seed {seed} call {i}: {t} {op} P={P} lens={lens} odd={odd} sodd={sodd} inplace={inplace}"
-        try:
-            _collective(torch_cuda, t, op, P, lens, seed + i, inplace=inplace, odd=odd, sodd=sodd)
-        except AssertionError as e:
-            raise AssertionError(f"{what}: {e}") from None
+        with D.named(what):
+            _collective(t, op, P, lens, seed + i, inplace=inplace, odd=odd, sodd=sodd)

@@ -28,34 +28,15 @@ import numpy as np
 import pytest
 
 import osgpu
+from support import gpu_doors as D
 from support import guarded as G
 from support import matrix_cases as X
 from support import rscatter_cases as C
 from support import scan_cases as S
 from support import uniform_cases as U
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (NULL means the
-    calling thread's stream to the launchers, which is not ordered after
-    torch's uploads)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 # ------------------------------------------------------------ a. raw launchers
@@ -84,15 +65,13 @@ def placements(kernel, t, P):
     return out
 
 
-class RawBatch:
-    """Every case of one (kernel, type): all ops in one arena, one upload, the
-    launches, one synchronize, one download.  Expected values are computed once
-    per (op, P) at the longest length and sliced."""
+class RawBatch(D.LauncherBatch):
+    """Every case of one (kernel, type): all ops in one arena.  Expected values
+    are computed once per (op, P) at the longest length and sliced."""
 
     def __init__(self, kernel, t):
-        self.kernel, self.t, self.s = kernel, t, X.esize(t)
-        self.arena = G.Arena()
-        self.cases = []
+        super().__init__(t)
+        self.kernel = kernel
         self.pool = {}
         self.full = {}
 
@@ -107,54 +86,29 @@ class RawBatch:
                         srcs = [self.arena.add(n * self.s, sph[p], self.pool[op, P][p][:n])
                                 for p in range(P)]
                         dsts = [self.arena.add(n * self.s, ph) for ph in dph]
-                        self.cases.append((op, P, n, ex, srcs, dsts, what))
+                        self.case(srcs, dsts, what, kernel=kernel, op=op, P=P, n=n, exclusive=ex)
 
-    def launch(self, torch):
-        self.arena.upload(torch)
-        sp = _stream(torch)
-        for op, P, n, ex, srcs, dsts, _ in self.cases:
-            d, s = [g.ptr for g in dsts], [g.ptr for g in srcs]
-            if self.kernel == "combine_shifted":
-                osgpu.combine_shifted(self.t, op, d[0], s, n, stream=sp)
-            elif self.kernel == "team_scan":
-                osgpu.team_scan(self.t, op, ex, d, s, n, stream=sp)
-            else:
-                osgpu.team_uniform(self.t, op, d, s, n, stream=sp)
-        torch.cuda.synchronize()
-        self.arena.download()
-        return self
+    def call(self, c, sp):
+        d, s = D.ptrs(c.dsts), D.ptrs(c.srcs)
+        if self.kernel == "combine_shifted":
+            osgpu.combine_shifted(self.t, c.op, d[0], s, c.n, stream=sp)
+        elif self.kernel == "team_scan":
+            osgpu.team_scan(self.t, c.op, c.exclusive, d, s, c.n, stream=sp)
+        else:
+            osgpu.team_uniform(self.t, c.op, d, s, c.n, stream=sp)
 
-    def want(self, op, P, q, n, ex):
-        key = (op, P)
+    def want(self, c, q):
+        key = (c.op, c.P)
         if key not in self.full:
-            pool = self.pool[key]
-            if self.kernel == "combine_shifted":
-                self.full[key] = C.fold_left(self.t, op, pool)
-            elif self.kernel == "team_scan":
-                self.full[key] = S.inclusive(self.t, op, pool)
-            else:
-                self.full[key] = U.value(self.t, op, pool)
+            fold = {"combine_shifted": C.fold_left, "team_scan": S.inclusive,
+                    "team_uniform": U.value}[self.kernel]
+            self.full[key] = fold(self.t, c.op, self.pool[key])
         full = self.full[key]
         if self.kernel != "team_scan":
-            return full[:n]
-        if ex and q == 0:
-            return np.repeat(S.identity(self.t, op), n)
-        return full[q - ex][:n]
-
-    def check(self):
-        t = self.t
-        for op, P, n, ex, srcs, dsts, what in self.cases:
-            what = f"{self.kernel} {t} {op} P={P} n={n} exclusive={ex} {what}"
-            for q, out in enumerate(dsts):
-                got = out.data().view(np.longdouble if t == "longdouble" else X.dtype(t))
-                bad = X.same_bits(t, got, self.want(op, P, q, n, ex))
-                assert bad is None, f"{what}: target {q}, element {bad} differs from the oracle"
-                if t == "longdouble":
-                    assert not out.data().reshape(-1, 16)[:, 10:].any(), \
-                        f"{what}: target {q}, long double padding not zero"
-                out.assert_guards(f"{what} target {q}")
-            for p, g in enumerate(srcs):
-                g.assert_unchanged(f"{what} source {p}")
+            return full[:c.n]
+        if c.exclusive and q == 0:
+            return np.repeat(S.identity(self.t, c.op), c.n)
+        return full[q - c.exclusive][:c.n]
 
 
 RAW = [(k, t) for k in X.RAW_KERNELS for t in X.RAW_TYPES[k]]

@@ -19,20 +19,13 @@ import pytest
 import oracle as O
 import osgpu
 from support import guarded
+from support.gpu_doors import stream, torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 # x87 80-bit long double runs on the GPU through the soft-float in x87.hpp
 LD_ON_GPU = True
 CASES = [c for c in O.load_cases() if LD_ON_GPU or c["type"] != "longdouble"]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 _TEAMS = {}
@@ -407,19 +400,6 @@ def test_staged_copy_streams_survive_extra_streams(torch_cuda):
     del side
 
 
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream, after draining the device: torch's default
-    stream has handle 0, and a NULL stream means "the calling thread's
-    stream" to osgpu_combine, which would not be ordered after torch's work."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
-
-
 def _dev(torch, arr):
     raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
     return torch.from_numpy(raw.copy()).to("cuda:0")
@@ -448,7 +428,7 @@ def test_combine_ragged_and_misaligned(torch_cuda, t, k):
             # osgpu_combine is asynchronous: enqueue it on torch's stream so
             # it is ordered after the uploads and the zero fill
             osgpu.combine(t, op, out.data_ptr() + shift_out * s,
-                          [b.data_ptr() + shift_in * s for b in bufs], n, _stream(torch))
+                          [b.data_ptr() + shift_in * s for b in bufs], n, stream(torch))
             torch.cuda.synchronize()
             got = out.cpu().numpy()[shift_out * s:]
             if t == "longdouble":
@@ -472,7 +452,7 @@ def test_longdouble_8byte_aligned_arrays(torch_cuda, op):
             for x in ins]
     out = torch.zeros(n * 16 + 8, dtype=torch.uint8, device="cuda:0")
     osgpu.combine("longdouble", op, out.data_ptr() + 8, [b.data_ptr() + 8 for b in bufs], n,
-                  _stream(torch))
+                  stream(torch))
     torch.cuda.synchronize()
     got = out.cpu().numpy()[8:].reshape(-1, 16)[:, :10].reshape(-1)
     assert np.array_equal(got, O.value_bytes(want).reshape(-1))
@@ -527,7 +507,7 @@ def test_large_config2_shape_properties(torch_cuda):
     b = torch.rand(n, dtype=torch.float64, device="cuda:0") + 1.0
     out = torch.empty_like(a)
     osgpu.combine("double", "sum", out.data_ptr(), [a.data_ptr(), b.data_ptr()], n,
-                  _stream(torch))
+                  stream(torch))
     torch.cuda.synchronize()
     idx = torch.randint(0, n, (1 << 16,), device="cuda:0")
     sa, sb, so = a[idx].cpu().numpy(), b[idx].cpu().numpy(), out[idx].cpu().numpy()
@@ -549,12 +529,12 @@ def test_config3_bitwise_full_size(torch_cuda):
     for op, ref in (("and", torch.bitwise_and), ("or", torch.bitwise_or),
                     ("xor", torch.bitwise_xor)):
         osgpu.combine("long", op, out.data_ptr(), [a.data_ptr(), b.data_ptr()], n,
-                      _stream(torch))
+                      stream(torch))
         torch.cuda.synchronize()
         assert torch.equal(out, ref(a, b)), op
     # xor is its own inverse: (a ^ b) ^ b == a
     osgpu.combine("long", "xor", out.data_ptr(), [out.data_ptr(), b.data_ptr()], n,
-                  _stream(torch))
+                  stream(torch))
     torch.cuda.synchronize()
     assert torch.equal(out, a)
 
@@ -772,7 +752,7 @@ def test_combine_multi_launch(torch_cuda, small_launches, t, k):
             bufs = [_dev(torch, np.concatenate([O.gen_input(t, shift, 5, "mixed"), x])) for x in ins]
             out = torch.zeros((n + shift) * s, dtype=torch.uint8, device="cuda:0")
             osgpu.combine(t, "sum", out.data_ptr() + shift * s,
-                          [b.data_ptr() + shift * s for b in bufs], n, _stream(torch))
+                          [b.data_ptr() + shift * s for b in bufs], n, stream(torch))
             torch.cuda.synchronize()
             got = out.cpu().numpy()[shift * s:]
             bad = np.nonzero(got.reshape(-1) != O.value_bytes(want).reshape(-1))[0]

@@ -38,42 +38,18 @@ over the full P * n sources, member m's block m sliced out).
 """
 import ctypes
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import osgpu
-from support import guarded as G
+from support import gpu_doors as D
 from support import rscatter_cases as C
+from support.gpu_doors import small_launches, torch_cuda  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 V = C.TILE_VECTORS
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (NULL means the
-    calling thread's stream to the launchers, which is not ordered after
-    torch's uploads)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 def lengths(t):
@@ -82,48 +58,30 @@ def lengths(t):
 
 
 # ------------------------------------------------------------ 1. raw launcher
-class Batch:
-    """Cases of one (type, op) in one arena: one upload, the launches, one
-    synchronize, one download."""
+class Batch(D.LauncherBatch):
+    """Cases of one (type, op): K inputs folded into one target."""
 
     def __init__(self, t, op, kmax, nmax, seed):
-        self.t, self.op, self.s = t, op, C.esize(t)
+        super().__init__(t)
+        self.op = op
         self.pool = C.inputs(t, op, kmax, nmax, seed)
-        self.want = {}      # K -> fold of pool[:K] at nmax
-        self.arena = G.Arena()
-        self.cases = []
+        self.fold = {}      # K -> fold of pool[:K] at nmax
 
     def add(self, K, n, tgt_phase, src_phases, what):
         srcs = [self.arena.add(n * self.s, src_phases[k], self.pool[k][:n]) for k in range(K)]
-        out = self.arena.add(n * self.s, tgt_phase)
-        self.cases.append((K, n, srcs, out, what))
+        self.case(srcs, [self.arena.add(n * self.s, tgt_phase)], what, op=self.op, K=K, n=n)
 
     def launch(self, torch, shifted=True):
-        self.arena.upload(torch)
-        sp = _stream(torch)
-        f = osgpu.combine_shifted if shifted else osgpu.combine
-        for K, n, srcs, out, _ in self.cases:
-            f(self.t, self.op, out.ptr, [g.ptr for g in srcs], n, stream=sp)
-        torch.cuda.synchronize()
-        self.arena.download()
-        return self
+        self.launcher = osgpu.combine_shifted if shifted else osgpu.combine
+        return super().launch(torch)
 
-    def check(self):
-        for K, n, srcs, out, what in self.cases:
-            what = f"{self.t} {self.op} K={K} n={n} {what}"
-            if K not in self.want:
-                self.want[K] = C.fold_left(self.t, self.op, self.pool[:K])
-            got = out.data().view(C.dtype(self.t)) if self.t != "longdouble" else out.data()
-            want = self.want[K][:n]
-            if self.t == "longdouble":
-                got = got.view(np.longdouble)
-                pad = out.data().reshape(-1, 16)[:, 10:]
-                assert not pad.any(), f"{what}: long double padding not zero"
-            bad = C.same_bits(self.t, got, want)
-            assert bad is None, f"{what}: element {bad} differs from the oracle's fold"
-            out.assert_guards(what + " target")
-            for k, g in enumerate(srcs):
-                g.assert_unchanged(f"{what} input {k}")
+    def call(self, c, sp):
+        self.launcher(self.t, self.op, c.dsts[0].ptr, D.ptrs(c.srcs), c.n, stream=sp)
+
+    def want(self, c, q):
+        if c.K not in self.fold:
+            self.fold[c.K] = C.fold_left(self.t, self.op, self.pool[:c.K])
+        return self.fold[c.K][:c.n]
 
 
 @pytest.mark.parametrize("t,op", C.PAIRS, ids=lambda x: x)
@@ -172,20 +130,6 @@ def test_launcher_equal_phases_match_osgpu_combine(torch_cuda):
         b.launch(torch_cuda, shifted=False).check()
 
 
-@pytest.fixture
-def small_launches(monkeypatch):
-    """At most 256 threads per launch (osgpu_test_max_launch_threads): at
-    K = 2 a launch holds two tiles, at K = 3 one."""
-    monkeypatch.setenv("OSGPU_TEST_HOOKS", "1")
-    L = osgpu.load()
-    L.osgpu_test_max_launch_threads.argtypes = [ctypes.c_longlong]
-
-    def set_limit(n):
-        assert L.osgpu_test_max_launch_threads(n) == 0, L.osgpu_last_error()
-    yield set_limit
-    assert L.osgpu_test_max_launch_threads(0) == 0
-
-
 @pytest.mark.parametrize("t,op", [("int", "sum"), ("short", "min"), ("double", "sum")],
                          ids=lambda x: x)
 def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
@@ -206,7 +150,7 @@ def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
                     b.add(K, (W - shift) % W + nvec * W + 1, shift * s, [0] * K,
                           f"limit {limit} shift {shift}")
         b.launch(torch_cuda).check()
-        res.append([c[3].data().copy() for c in b.cases])
+        res.append([c.dsts[0].data().copy() for c in b.cases])
     for one, many in zip(*res):
         assert np.array_equal(one, many)
 
@@ -254,46 +198,14 @@ def test_launcher_routes(torch_cuda, small_launches):
 
 
 # ---------------------------------------------------- 2. collective, PE threads
-def _heap_layout(t, P, n, target_elem_off=0):
-    """(source offset, target offset, heap bytes): the target in its own
-    4 KiB-aligned area behind the source, shifted by target_elem_off elements."""
-    s = C.esize(t)
-    src_bytes = P * n * s
-    toff = (src_bytes + 4095) // 4096 * 4096 + 4096 + target_elem_off * s
-    return 0, toff, toff + n * s + 8192
+RSCATTER = D.Door("reduce-scatter", C.run, C.expected, src_elems=lambda n, PE_size: PE_size * n)
 
 
-def _collective(torch, t, op, npes, n, seed, PE_start=0, log=0, PE_size=None, target_elem_off=0,
-                overlap_block=None):
-    """One call on a fresh team; checks every member's block, the bytes
-    round its target, the path and (in Team._on_members) pSync."""
-    from support import team as T
-    PE_size = npes if PE_size is None else PE_size
-    s = C.esize(t)
-    soff, toff, hb = _heap_layout(t, PE_size, n, target_elem_off)
-    if overlap_block is not None:   # the target on top of block `overlap_block` of the source
-        toff = soff + (overlap_block * n + target_elem_off) * s
-    tm = T.Team(npes, hb, device=True)
-    src = C.inputs(t, op, npes, PE_size * n, seed)
-    for pe in range(npes):
-        tm.fill(pe, 0, hb, 0xC3)
-        tm.write(pe, soff, src[pe])
-    before = {pe: tm.read(pe, 0, hb) for pe in range(npes)}
-    members = C.run(tm, t, op, toff, soff, n, PE_start, log, PE_size)
-    want = C.expected(t, op, src, n, PE_start, log, PE_size)
-    for pe in range(npes):
-        after = tm.read(pe, 0, hb)
-        if pe not in members:
-            assert np.array_equal(after, before[pe]), f"PE {pe} is not a member"
-            continue
-        got = after[toff:toff + n * s].view(C.dtype(t))
-        bad = C.same_bits(t, got, want[pe])
-        what = f"{t} {op} P={PE_size} n={n} PE {pe}"
-        assert bad is None, f"{what}: element {bad} differs"
-        assert np.array_equal(after[:toff], before[pe][:toff]), f"{what}: bytes before the target"
-        assert np.array_equal(after[toff + n * s:], before[pe][toff + n * s:]), \
-            f"{what}: bytes after the target"
-        assert tm.last_paths[pe] == "pull", tm.last_paths
+def _collective(t, op, npes, n, seed, PE_start=0, log=0, PE_size=None, target_elem_off=0,
+                overlap_block=None, path="pull", **kw):
+    """overlap_block: the target on top of that block of the source."""
+    D.collective(RSCATTER, t, op, npes, n, seed, PE_start, log, PE_size, path, target_elem_off,
+                 on_source=None if overlap_block is None else overlap_block * n, **kw)
 
 
 @pytest.mark.parametrize("P", [2, 3, 8])
@@ -301,33 +213,33 @@ def _collective(torch, t, op, npes, n, seed, PE_start=0, log=0, PE_size=None, ta
 def test_collective_device_heaps(torch_cuda, t, op, P):
     W = 16 // C.esize(t)
     for n in (1, 1001, V * W + 3):
-        _collective(torch_cuda, t, op, P, n, 0xD0 + P)
+        _collective(t, op, P, n, 0xD0 + P)
 
 
 def test_collective_strided_active_set(torch_cuda):
-    _collective(torch_cuda, "double", "sum", 8, 1001, 5, PE_start=1, log=1, PE_size=3)
-    _collective(torch_cuda, "short", "min", 6, 259, 6, PE_start=0, log=1, PE_size=3)
+    _collective("double", "sum", 8, 1001, 5, PE_start=1, log=1, PE_size=3)
+    _collective("short", "min", 6, 259, 6, PE_start=0, log=1, PE_size=3)
 
 
 @pytest.mark.parametrize("block", [0, 1, 2])
 def test_collective_in_place(torch_cuda, block):
     """The target on top of a block of the source (the caller's own block on
     one member, another's on the others)."""
-    _collective(torch_cuda, "float", "prod", 3, 1001, 9 + block, overlap_block=block)
-    _collective(torch_cuda, "int", "sum", 3, 7, 19 + block, overlap_block=block)
+    _collective("float", "prod", 3, 1001, 9 + block, overlap_block=block)
+    _collective("int", "sum", 3, 7, 19 + block, overlap_block=block)
 
 
 def test_collective_target_sub_view(torch_cuda):
     """A target that starts an odd number of elements into its array."""
     for t, op in (("short", "min"), ("int", "sum"), ("double", "sum"), ("half", "sum")):
-        _collective(torch_cuda, t, op, 3, 1001, 0x5B, target_elem_off=3)
+        _collective(t, op, 3, 1001, 0x5B, target_elem_off=3)
 
 
 def test_collective_long_double_and_single_member(torch_cuda):
-    _collective(torch_cuda, "longdouble", "sum", 3, 257, 3)
-    _collective(torch_cuda, "complexd", "prod", 2, 129, 4)
-    _collective(torch_cuda, "int", "sum", 1, 1001, 5)          # PE_size == 1: a copy
-    _collective(torch_cuda, "double", "sum", 4, 11, 6, PE_start=2, PE_size=1)
+    _collective("longdouble", "sum", 3, 257, 3)
+    _collective("complexd", "prod", 2, 129, 4)
+    _collective("int", "sum", 1, 1001, 5)          # PE_size == 1: a copy
+    _collective("double", "sum", 4, 11, 6, PE_start=2, PE_size=1)
 
 
 # ------------------------------------------------------ host heaps (need a GPU)
@@ -336,66 +248,21 @@ def test_collective_host_heaps(torch_cuda, path):
     """Host fold and GETMEM (forced by the fold limit / osgpu_set_host_path;
     a forced STAGED takes GETMEM): blocks, a strided set, overlap with the
     caller's own and another block, a chunk smaller than the block."""
-    from support import team as T
-    L = osgpu.load()
     cases = [("double", "sum", 3, 0, 0, 3, 1001, None), ("short", "min", 2, 0, 0, 2, 5, None),
              ("float", "prod", 8, 1, 1, 3, 300, None), ("int", "sum", 3, 0, 0, 3, 1001, 0),
              ("long", "xor", 3, 0, 0, 3, 64, 1), ("half", "sum", 3, 0, 0, 3, 1001, None),
              ("longdouble", "sum", 1, 0, 0, 1, 9, None), ("complexf", "prod", 1, 0, 0, 1, 33, None)]
-    try:
+    with D.host_heaps(path) as (force, team, ran):
         for t, op, npes, start, log, size, n, ov in cases:
-            s = C.esize(t)
-            soff, toff, hb = _heap_layout(t, size, n)
-            if ov is not None:
-                toff = soff + ov * n * s
-            tm = T.Team(npes, hb, device=False, host_fold=(path == "host_fold"))
-            if path != "host_fold":
-                assert L.osgpu_set_host_path(osgpu.HOST_PATHS[path]) == 0
-                assert L.osgpu_set_host_chunk_bytes(2048) == 0
-            src = C.inputs(t, op, npes, size * n, 31 + n)
-            for pe in range(npes):
-                tm.fill(pe, 0, hb, 0xC3)
-                tm.write(pe, soff, src[pe])
-            before = {pe: tm.read(pe, 0, hb) for pe in range(npes)}
-            members = C.run(tm, t, op, toff, soff, n, start, log, size)
-            want = C.expected(t, op, src, n, start, log, size)
-            for pe in members:
-                after = tm.read(pe, 0, hb)
-                bad = C.same_bits(t, after[toff:toff + n * s].view(C.dtype(t)), want[pe])
-                assert bad is None, f"{path} {t} {op} P={size} n={n} PE {pe}: element {bad}"
-                assert np.array_equal(after[:toff], before[pe][:toff])
-                assert np.array_equal(after[toff + n * s:], before[pe][toff + n * s:])
-                assert tm.last_paths[pe] == ("host_fold" if path == "host_fold" else "getmem")
-    finally:
-        L.osgpu_set_host_path(-1)
-        L.osgpu_set_host_chunk_bytes(-1)
-        L.osgpu_set_host_fold_max_bytes(-1)
+            force()
+            _collective(t, op, npes, n, 31 + n, start, log, size, overlap_block=ov, path=ran, **team)
 
 
 # ------------------------------------------------------------ 3. two processes
 def test_two_processes_one_gpu(torch_cuda, tmp_path):
     """2 ranks, one process each, heaps made by osgpu_heap_create: the pull
     path over a peer mapping (tests/support/rscatter_mp_worker.py)."""
-    worker = os.path.join(ROOT, "tests", "support", "rscatter_mp_worker.py")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path)],
-                              env=dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
-                                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                                       PYTHONUNBUFFERED="1"),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for r in range(2)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=150)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and "RSCATTER_MP_OK" in o, f"rank {r}:\n{o[-3000:]}"
+    D.run_ranks("rscatter_mp_worker.py", tmp_path, "RSCATTER_MP_OK")
 
 
 # -------------------------------------------------------------------- 4. fuzz
@@ -412,8 +279,6 @@ def test_fuzz_30_calls(torch_cuda):
         shift = int(rng.integers(0, W)) if W > 1 else 0
         overlap = bool(rng.integers(2)) and P > 1
         what = f"seed {seed} call {i}: {t} {op} P={P} n={n} shift={shift} overlap={overlap}"
-        try:
-            _collective(torch_cuda, t, op, P, n, seed + i, target_elem_off=shift,
+        with D.named(what):
+            _collective(t, op, P, n, seed + i, target_elem_off=shift,
                         overlap_block=int(rng.integers(P)) if overlap else None)
-        except AssertionError as e:
-            raise AssertionError(f"{what}: {e}") from None

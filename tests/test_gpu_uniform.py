@@ -29,46 +29,22 @@ Expected values: tests/support/uniform_cases.py.  The inputs of the collective
 tests (n = 1001, seed 0xD0 + P) are the ones tests/test_uniform_ref.py shows a
 caller-first fold to differ on.
 """
-import ctypes
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import osgpu
+from support import gpu_doors as D
 from support import guarded as G
 from support import uniform_cases as C
+from support.gpu_doors import small_launches, torch_cuda  # noqa: F401  (fixtures)
 from test_x87_softfloat import raw_random
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUB = C.SUB_VECTORS
 RAW_PAIRS = C.PAIRS + [("float", "max")]    # float max: NaNs and signed zeros (the edge inputs)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-_S = []
-
-
-def _stream(torch):
-    """A non-default torch stream after draining the device (NULL means the
-    calling thread's stream to the launchers, which is not ordered after
-    torch's uploads)."""
-    torch.cuda.synchronize()
-    if not _S:
-        _S.append(torch.cuda.Stream())
-    return _S[0].cuda_stream
 
 
 def lengths(t, P):
@@ -78,53 +54,30 @@ def lengths(t, P):
 
 
 # ------------------------------------------------------------ 1. raw launcher
-class Batch:
-    """Cases of one (type, op) in one arena: one upload, the launches, one
-    synchronize, one download.  The expected value of P members is computed
+class Batch(D.LauncherBatch):
+    """Cases of one (type, op).  The expected value of P members is computed
     once at the longest length and sliced."""
 
     def __init__(self, t, op, nmax, seed, pool=None):
-        self.t, self.op, self.s = t, op, C.esize(t)
+        super().__init__(t)
+        self.op = op
         self.pool = C.inputs(t, op, 8, nmax, seed) if pool is None else pool
         self.val = {}       # P -> the uniform value of P members at nmax
-        self.arena = G.Arena()
-        self.cases = []
 
     def add(self, P, n, src_phases, dst_phases, what):
         srcs = [self.arena.add(n * self.s, src_phases[p], self.pool[p][:n]) for p in range(P)]
         dsts = [self.arena.add(n * self.s, dst_phases[q]) for q in range(P)]
-        self.cases.append((P, n, srcs, dsts, what))
+        self.case(srcs, dsts, what, op=self.op, P=P, n=n)
 
-    def launch(self, torch):
-        self.arena.upload(torch)
-        sp = _stream(torch)
-        for P, n, srcs, dsts, _ in self.cases:
-            osgpu.team_uniform(self.t, self.op, [g.ptr for g in dsts], [g.ptr for g in srcs], n,
-                               stream=sp)
-        torch.cuda.synchronize()
-        self.arena.download()
-        return self
+    def call(self, c, sp):
+        osgpu.team_uniform(self.t, self.op, D.ptrs(c.dsts), D.ptrs(c.srcs), c.n, stream=sp)
 
-    def want(self, P, n):
-        if P not in self.val:
-            self.val[P] = C.value(self.t, self.op, self.pool[:P])
-        return self.val[P][:n]
+    def want(self, c, q):
+        if c.P not in self.val:
+            self.val[c.P] = C.value(self.t, self.op, self.pool[:c.P])
+        return self.val[c.P][:c.n]
 
-    def check(self):
-        for P, n, srcs, dsts, what in self.cases:
-            what = f"{self.t} {self.op} P={P} n={n} {what}"
-            for q, out in enumerate(dsts):
-                got = out.data().view(C.dtype(self.t))
-                bad = C.same_bits(self.t, got, self.want(P, n))
-                assert bad is None, f"{what}: member {q}, element {bad} differs from the oracle"
-                assert np.array_equal(out.data(), dsts[0].data()), \
-                    f"{what}: members {q} and 0 hold different bytes"
-                if self.t == "longdouble":
-                    assert not out.data().reshape(-1, 16)[:, 10:].any(), \
-                        f"{what}: member {q}, long double padding not zero"
-                out.assert_guards(f"{what} target {q}")
-            for p, g in enumerate(srcs):
-                g.assert_unchanged(f"{what} source {p}")
+    check_case = staticmethod(D.targets_identical)
 
 
 @pytest.mark.parametrize("t,op", RAW_PAIRS, ids=lambda x: x)
@@ -157,19 +110,6 @@ def test_launcher_phases(torch_cuda, t, op):
     b.launch(torch_cuda).check()
 
 
-@pytest.fixture
-def small_launches(monkeypatch):
-    """osgpu_test_max_launch_threads: the multi-launch path at small sizes."""
-    monkeypatch.setenv("OSGPU_TEST_HOOKS", "1")
-    L = osgpu.load()
-    L.osgpu_test_max_launch_threads.argtypes = [ctypes.c_longlong]
-
-    def set_limit(n):
-        assert L.osgpu_test_max_launch_threads(n) == 0, L.osgpu_last_error()
-    yield set_limit
-    assert L.osgpu_test_max_launch_threads(0) == 0
-
-
 @pytest.mark.parametrize("t,op", [("int", "sum"), ("double", "sum"), ("half", "sum")],
                          ids=lambda x: x)
 def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
@@ -187,7 +127,7 @@ def test_launcher_multi_launch(torch_cuda, small_launches, t, op):
             b.add(P, n, [0] * P, [0] * P, f"limit {limit}")
             b.add(P, n + W - 1, [16 - s] * P, [16 - s] * P, f"limit {limit} edges")
         b.launch(torch_cuda).check()
-        res.append([d.data().copy() for c in b.cases for d in c[3]])
+        res.append([d.data().copy() for c in b.cases for d in c.dsts])
     for one, many in zip(*res):
         assert np.array_equal(one, many)
 
@@ -234,112 +174,63 @@ def test_launcher_bad_arguments(torch_cuda):
 
 
 # ---------------------------------------------------- 2. collective, PE threads
-def _heap_layout(t, n, target_elem_off=0):
-    """(source offset, target offset, heap bytes): the target in its own
-    4 KiB-aligned area behind the source, shifted by target_elem_off elements."""
-    s = C.esize(t)
-    toff = (n * s + 4095) // 4096 * 4096 + 4096 + target_elem_off * s
-    return 0, toff, toff + n * s + 8192
+UNIFORM = D.Door("uniform", C.run, lambda t, op, src, n, *active: C.expected(t, op, src, *active),
+                 extra=D.same_bytes_as_first)
 
 
-def _check_members(tm, t, op, src, n, soff, toff, hb, before, members, start, log, size, path,
-                   what):
-    s = C.esize(t)
-    want = C.expected(t, op, src, start, log, size)
-    first = None
-    for pe in range(tm.npes):
-        after = tm.read(pe, 0, hb)
-        if pe not in members:
-            assert np.array_equal(after, before[pe]), f"{what}: PE {pe} is not a member"
-            continue
-        w = f"{what} PE {pe}"
-        got = after[toff:toff + n * s]
-        bad = C.same_bits(t, got.view(C.dtype(t)), want[pe])
-        assert bad is None, f"{w}: element {bad} differs"
-        if t == "longdouble":
-            assert not got.reshape(-1, 16)[:, 10:].any(), f"{w}: long double padding not zero"
-        first = got if first is None else first
-        assert np.array_equal(got, first), f"{w}: not the bytes of member {members[0]}"
-        assert np.array_equal(after[:toff], before[pe][:toff]), f"{w}: bytes before the target"
-        assert np.array_equal(after[toff + n * s:], before[pe][toff + n * s:]), \
-            f"{w}: bytes after the target"
-        if path is not None:
-            assert tm.last_paths[pe] == path, (w, tm.last_paths)
-
-
-def _collective(torch, t, op, npes, n, seed, PE_start=0, log=0, PE_size=None, path="team",
-                target_elem_off=0, in_place=False, device=True, host_fold=False):
-    """One call on a fresh team; checks every member's result, the bytes
-    round its target, the path and (in Team._on_members) pSync."""
-    from support import team as T
-    PE_size = npes if PE_size is None else PE_size
-    soff, toff, hb = _heap_layout(t, n, target_elem_off)
-    if in_place:
-        toff = soff + target_elem_off * C.esize(t)
-        hb += target_elem_off * C.esize(t)
-    tm = T.Team(npes, hb, device=device, host_fold=host_fold)
-    src = C.inputs(t, op, npes, n, seed)
-    for pe in range(npes):
-        tm.fill(pe, 0, hb, 0xC3)
-        tm.write(pe, soff, src[pe])
-    before = {pe: tm.read(pe, 0, hb) for pe in range(npes)}
-    members = C.run(tm, t, op, toff, soff, n, PE_start, log, PE_size)
-    _check_members(tm, t, op, src, n, soff, toff, hb, before, members, PE_start, log, PE_size,
-                   path, f"{t} {op} P={PE_size} n={n}")
+def _collective(t, op, npes, n, seed, PE_start=0, log=0, PE_size=None, in_place=False, **kw):
+    D.collective(UNIFORM, t, op, npes, n, seed, PE_start, log, PE_size,
+                 on_source=0 if in_place else None, **kw)
 
 
 @pytest.mark.parametrize("P", [2, 3, 8])
 @pytest.mark.parametrize("t,op", C.PAIRS + [("longdouble", "sum")], ids=lambda x: x)
 def test_collective_device_heaps(torch_cuda, t, op, P):
     for n in sorted({1, P - 1, 1001, P * C.tile_elems(t, P) + 3}):
-        _collective(torch_cuda, t, op, P, n, 0xD0 + P)
+        _collective(t, op, P, n, 0xD0 + P)
 
 
 def test_collective_discriminating_pairs(torch_cuda):
     """float max, the one pair of tests/test_uniform_ref.py's discrimination
     condition outside PAIRS, on the same inputs."""
     for P in (3, 8):
-        _collective(torch_cuda, "float", "max", P, 1001, 0xD0 + P)
+        _collective("float", "max", P, 1001, 0xD0 + P)
 
 
 def test_collective_strided_active_set(torch_cuda):
-    _collective(torch_cuda, "double", "sum", 8, 1001, 5, PE_start=1, log=1, PE_size=3)
-    _collective(torch_cuda, "short", "min", 6, 259, 6, PE_start=0, log=1, PE_size=3)
-    _collective(torch_cuda, "longdouble", "prod", 5, 77, 7, PE_start=0, log=2, PE_size=2)
+    _collective("double", "sum", 8, 1001, 5, PE_start=1, log=1, PE_size=3)
+    _collective("short", "min", 6, 259, 6, PE_start=0, log=1, PE_size=3)
+    _collective("longdouble", "prod", 5, 77, 7, PE_start=0, log=2, PE_size=2)
 
 
 def test_collective_pull_forms(torch_cuda):
     """OSGPU_PATH_PULL, in-place overlap and 9 members (the team form stops
     at 8) take the pull form."""
-    L = osgpu.load()
-    try:
-        assert L.osgpu_set_path(osgpu.PATH_PULL) == 0
-        _collective(torch_cuda, "double", "sum", 3, 1001, 0xD0 + 3, path="pull")
-        _collective(torch_cuda, "half", "sum", 8, 1001, 0xD0 + 8, path="pull")
-        _collective(torch_cuda, "longdouble", "sum", 3, 257, 25, path="pull")
-    finally:
-        L.osgpu_set_path(osgpu.PATH_AUTO)
-    _collective(torch_cuda, "float", "prod", 3, 1001, 0xD0 + 3, path="pull", in_place=True)
-    _collective(torch_cuda, "int", "sum", 4, 7, 24, path="pull", in_place=True, target_elem_off=3)
-    _collective(torch_cuda, "longdouble", "max", 2, 33, 26, path="pull", in_place=True)
-    _collective(torch_cuda, "int", "sum", 9, 1001, 27, path="pull")
-    _collective(torch_cuda, "float", "max", 9, 130, 28, path="pull")
-    _collective(torch_cuda, "double", "sum", 9, 1001, 29, path="pull")
+    with D.forced_path(osgpu.PATH_PULL):
+        _collective("double", "sum", 3, 1001, 0xD0 + 3, path="pull")
+        _collective("half", "sum", 8, 1001, 0xD0 + 8, path="pull")
+        _collective("longdouble", "sum", 3, 257, 25, path="pull")
+    _collective("float", "prod", 3, 1001, 0xD0 + 3, path="pull", in_place=True)
+    _collective("int", "sum", 4, 7, 24, path="pull", in_place=True, target_elem_off=3)
+    _collective("longdouble", "max", 2, 33, 26, path="pull", in_place=True)
+    _collective("int", "sum", 9, 1001, 27, path="pull")
+    _collective("float", "max", 9, 130, 28, path="pull")
+    _collective("double", "sum", 9, 1001, 29, path="pull")
 
 
 def test_collective_single_member(torch_cuda):
     """PE_size == 1: a copy of the source."""
-    _collective(torch_cuda, "int", "sum", 1, 1001, 5, path=None)
-    _collective(torch_cuda, "double", "min", 4, 11, 6, PE_start=2, PE_size=1, path=None)
-    _collective(torch_cuda, "longdouble", "prod", 1, 9, 7, path=None)
-    _collective(torch_cuda, "short", "and", 1, 77, 8, path=None, in_place=True)
+    _collective("int", "sum", 1, 1001, 5, path=None)
+    _collective("double", "min", 4, 11, 6, PE_start=2, PE_size=1, path=None)
+    _collective("longdouble", "prod", 1, 9, 7, path=None)
+    _collective("short", "and", 1, 77, 8, path=None, in_place=True)
 
 
 def test_collective_target_sub_view(torch_cuda):
     """A target an odd number of elements into its array: its phase differs
     from the sources', the team path's element-granular kernel."""
     for t, op in (("short", "min"), ("int", "sum"), ("half", "sum"), ("float", "prod")):
-        _collective(torch_cuda, t, op, 3, 1001, 0xD0 + 3, target_elem_off=3)
+        _collective(t, op, 3, 1001, 0xD0 + 3, target_elem_off=3)
 
 
 # ------------------------------------------------------ 3. host heaps (need a GPU)
@@ -348,24 +239,15 @@ def test_collective_host_heaps(torch_cuda, path):
     """Host fold and GETMEM (forced by the fold limit / osgpu_set_host_path; a
     forced STAGED takes GETMEM), the chunk below the array size; a strided
     set, overlap, one member, long double."""
-    L = osgpu.load()
     cases = [("double", "sum", 3, 0, 0, 3, 1001, False), ("short", "min", 2, 0, 0, 2, 5, False),
              ("float", "prod", 8, 1, 1, 3, 700, False), ("int", "sum", 3, 0, 0, 3, 1001, True),
              ("half", "sum", 3, 0, 0, 3, 1501, False), ("longdouble", "sum", 3, 0, 0, 3, 300, False),
              ("longdouble", "max", 1, 0, 0, 1, 9, False), ("complexf", "prod", 2, 0, 0, 2, 333, True),
              ("float", "max", 8, 0, 0, 8, 1001, False)]
-    ran = "host_fold" if path == "host_fold" else "getmem"
-    try:
+    with D.host_heaps(path) as (force, team, ran):
         for t, op, npes, start, log, size, n, ov in cases:
-            if path != "host_fold":
-                assert L.osgpu_set_host_path(osgpu.HOST_PATHS[path]) == 0
-                assert L.osgpu_set_host_chunk_bytes(2048) == 0
-            _collective(torch_cuda, t, op, npes, n, 0xD0 + size, start, log, size, path=ran,
-                        in_place=ov, device=False, host_fold=(path == "host_fold"))
-    finally:
-        L.osgpu_set_host_path(-1)
-        L.osgpu_set_host_chunk_bytes(-1)
-        L.osgpu_set_host_fold_max_bytes(-1)
+            force()
+            _collective(t, op, npes, n, 0xD0 + size, start, log, size, path=ran, in_place=ov, **team)
 
 
 # ------------------------------------------------------------ 4. two processes
@@ -373,26 +255,7 @@ def test_two_processes_one_gpu(torch_cuda, tmp_path):
     """2 ranks, one process each, heaps made by osgpu_heap_create: the uniform
     kernel writes a peer's target through a mapping of another process's
     memory (tests/support/uniform_mp_worker.py)."""
-    worker = os.path.join(ROOT, "tests", "support", "uniform_mp_worker.py")
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = [subprocess.Popen([sys.executable, worker, str(tmp_path)],
-                              env=dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
-                                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                                       PYTHONUNBUFFERED="1"),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-             for r in range(2)]
-    outs = []
-    for p in procs:
-        try:
-            outs.append(p.communicate(timeout=150)[0])
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-    for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and "UNIFORM_MP_OK" in o, f"rank {r}:\n{o[-3000:]}"
+    D.run_ranks("uniform_mp_worker.py", tmp_path, "UNIFORM_MP_OK")
 
 
 # -------------------------------------------------------------------- 5. fuzz
@@ -411,8 +274,6 @@ def test_fuzz_30_calls(torch_cuda):
         overlap = bool(rng.integers(2))
         team = P >= 2 and not overlap
         what = f"seed {seed} call {i}: {t} {op} P={P} n={n} shift={shift} overlap={overlap}"
-        try:
-            _collective(torch_cuda, t, op, P, n, seed + i, target_elem_off=shift,
+        with D.named(what):
+            _collective(t, op, P, n, seed + i, target_elem_off=shift,
                         in_place=overlap, path="team" if team else "pull")
-        except AssertionError as e:
-            raise AssertionError(f"{what}: {e}") from None

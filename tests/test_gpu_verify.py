@@ -14,18 +14,11 @@ import numpy as np
 import pytest
 
 import osgpu
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 M64 = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def _mix64(z):

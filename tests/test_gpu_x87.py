@@ -21,19 +21,12 @@ import pytest
 
 import oracle as O
 import osgpu
+from support.gpu_doors import torch_cuda  # noqa: F401  (fixture)
 from test_x87_softfloat import _deep_cancel_pairs, _pairs, near_bounds_srcs, raw_random
 
 pytestmark = pytest.mark.gpu
 
 OPS = ("sum", "prod", "max", "min")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
 
 
 def _dev(torch, arr):

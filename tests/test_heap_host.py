@@ -17,7 +17,7 @@ import subprocess
 
 import pytest
 
-from support import heap_host_build
+from support import host_check_build
 
 CASES = ["board1", "board2", "board5", "fds1", "fds64", "fds65", "fds129", "idle_server",
          "no_server", "truncated", "chunks", "report"]
@@ -25,7 +25,7 @@ CASES = ["board1", "board2", "board5", "fds1", "fds64", "fds65", "fds129", "idle
 
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return heap_host_build.build(san=request.param == "san")
+    return host_check_build.build("heap_host", san=request.param == "san")
 
 
 @pytest.mark.parametrize("case", CASES)

@@ -19,12 +19,12 @@ import pytest
 
 import osgpu
 from support import loc_cases as C
-from support import loc_host_build
+from support import host_check_build
 
 
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return loc_host_build.build(san=request.param == "san")
+    return host_check_build.build("loc_host", san=request.param == "san")
 
 
 def record(t, op, vals, locs=None, member=None):

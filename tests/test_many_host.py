@@ -20,14 +20,14 @@ import sys
 import pytest
 
 import osgpu
-from support import many_host_build
+from support import host_check_build
 
 CASES = ["routes", "packing", "overlap", "fold1", "fold3", "fold8", "fold_empty"]
 
 
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return many_host_build.build(san=request.param == "san")
+    return host_check_build.build("many_host", san=request.param == "san")
 
 
 @pytest.mark.parametrize("case", CASES)

@@ -26,7 +26,7 @@ import pytest
 
 import oracle as O
 import osgpu
-from support import fast_fold_build
+from support import host_check_build
 from support import half_ref as R
 from support import matrix_cases as X
 
@@ -171,7 +171,7 @@ def test_door_cases_lay_out_disjoint_areas():
 # ----------------------------------------------------- 3. the fast route
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return fast_fold_build.build(san=request.param == "san")
+    return host_check_build.build("fast_fold", san=request.param == "san")
 
 
 def test_fast_fold_premise(program):

@@ -11,14 +11,14 @@ import subprocess
 
 import pytest
 
-from support import rscatter_host_build
+from support import host_check_build
 
 CASES = ["blocks", "chunks", "fold1", "fold3", "fold8", "fold_empty"]
 
 
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return rscatter_host_build.build(san=request.param == "san")
+    return host_check_build.build("rscatter_host", san=request.param == "san")
 
 
 @pytest.mark.parametrize("case", CASES)

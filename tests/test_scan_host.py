@@ -11,14 +11,14 @@ import subprocess
 
 import pytest
 
-from support import scan_host_build
+from support import host_check_build
 
 CASES = ["prefix", "bytes", "chunks", "identity"]
 
 
 @pytest.fixture(scope="module", params=["plain", "san"])
 def program(request):
-    return scan_host_build.build(san=request.param == "san")
+    return host_check_build.build("scan_host", san=request.param == "san")
 
 
 @pytest.mark.parametrize("case", CASES)
