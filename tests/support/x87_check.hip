@@ -51,6 +51,18 @@ extern "C" int x87check_op(int op, const void *a, const void *b, void *out, size
     return 0;
 }
 
+// the near-exponent gate of team_fold_sum_prod: 0 kNearSpread, 1 kNearEmin,
+// 2 kNearEmax (tests/support/x87_wave_cases.py restates the gate from these)
+extern "C" int x87check_gate(int which)
+{
+    switch (which) {
+    case 0: return (int) kNearSpread;
+    case 1: return (int) kNearEmin;
+    case 2: return (int) kNearEmax;
+    }
+    return -1;
+}
+
 // every member's result of a P-PE sum / prod / max / min, as the team kernel
 // folds them (x87.hpp team_fold_sum_prod, team_fold_minmax): srcs[p] and dsts[p] are arrays of n 16-B
 // elements

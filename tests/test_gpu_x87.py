@@ -11,8 +11,12 @@ double ops (src/shmemu/miscops.c:30,98, native x87 on the host) directly.
 * the team kernel (osgpu_team_combine: every member's own fold order,
   src/reductions.c:79-111) at 5 and 8 members on random significands with
   random signs and exponents 2^-3..2^3 -- the data of the long double rate
-  measurements (tools/ld_team_rate.py), where every round takes the general
-  fast add -- and on the same data with one sign.
+  measurements (tools/ld_team_rate.py): every wave passes the near-exponent
+  gate (x87.hpp kNearSpread), so the rounds take add_near (F_NEAR) -- and on
+  the same data with one sign, add_same_near (F_SAME_NEAR); products take
+  mul_fast;
+* the gate's edges per wave (near_bounds_srcs).  Every fold mode at every
+  member count, wave by wave: tests/test_gpu_x87_waves.py.
 """
 import ctypes
 

@@ -13,6 +13,8 @@ import pytest
 
 import oracle as O
 from support import team as T
+from support.x87_wave_cases import (TIE_POOL, _deep_cancel_pairs, _pairs, equal_opposite_operands,  # noqa: F401
+                                    raw_random, tie_pairs)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 OPS = ((0, "sum"), (1, "prod"), (5, "max"), (6, "min"),
@@ -29,30 +31,6 @@ def soft(L, op, a, b):
     out = np.zeros_like(a)
     assert L.x87check_op(op, a.ctypes.data, b.ctypes.data, out.ctypes.data, a.size) == 0
     return out
-
-
-def raw_random(n, seed, mode):
-    r = O.splitmix64(seed, n)
-    r2 = O.splitmix64(seed ^ 0x77, n)
-    m = r.copy()
-    e = r2 & np.uint64(0x7FFF)
-    if mode == "normal":
-        m |= np.uint64(1 << 63)
-    elif mode == "near":       # operands within 2^65 of each other around 1
-        e = np.uint64(16383) + (r2 % np.uint64(130)) - np.uint64(65)
-        m |= np.uint64(1 << 63)
-    elif mode == "low":        # denormal / pseudo-denormal / tiny normals
-        e = r2 % np.uint64(70)
-        m |= np.uint64(1 << 63) * ((r2 >> np.uint64(20)) & np.uint64(1))
-    elif mode == "high":       # overflow range
-        e = np.uint64(0x7FFF) - (r2 % np.uint64(70))
-        m |= np.uint64(1 << 63)
-    s = (r2 >> np.uint64(40)) & np.uint64(1)
-    se = (e | (s << np.uint64(15))).astype(np.uint16)
-    arr = np.zeros((n, 16), np.uint8)
-    arr[:, :8] = m.view(np.uint8).reshape(n, 8)
-    arr[:, 8:10] = se.view(np.uint8).reshape(n, 2)
-    return arr.reshape(-1).view(np.longdouble)
 
 
 def check(L, a, b, use_ref):
@@ -91,70 +69,6 @@ def test_cancellation(x87):
     check(x87, x, y, use_ref=O.ref_lib() is not None)
 
 
-def _pairs(where, n=60_000):
-    r = O.splitmix64(77, 4 * n).reshape(4, n)
-    base_e = {"unit": 16383, "underflow": 3, "overflow": 0x7FFE - 1}[where]
-    diffs = np.array([0, 1, 2, 3, 29, 30, 31, 32, 62, 63, 64, 65, 66, 67, 70, 120, 200], np.int64)
-    d = diffs[r[0] % np.uint64(diffs.size)]
-    ea = np.full(n, base_e, np.int64) + (r[1] % np.uint64(3)).astype(np.int64) - 1
-    eb = np.clip(ea - d, 1, 0x7FFE)
-    # significands: random, or 2^63 + small, or 2^64 - small (seams of the
-    # borrow / carry cases)
-    kind = r[2] % np.uint64(3)
-    small = r[3] & np.uint64(0xFF)
-    top = np.uint64(1 << 63)
-    ma = np.where(kind == 0, r[2] | top, np.where(kind == 1, top + small,
-                                                  np.uint64((1 << 64) - 1) - small))
-    mb = np.where(kind == 2, r[3] | top, np.where(kind == 1, np.uint64((1 << 64) - 1) - small,
-                                                  top + small))
-    sa = (r[1] >> np.uint64(7)) & np.uint64(1)
-    sb = (r[1] >> np.uint64(9)) & np.uint64(1)
-
-    def pack(m, e, s):
-        arr = np.zeros((n, 16), np.uint8)
-        arr[:, :8] = m.astype(np.uint64).view(np.uint8).reshape(n, 8)
-        se = (e.astype(np.uint64) | (s << np.uint64(15))).astype(np.uint16)
-        arr[:, 8:10] = se.view(np.uint8).reshape(n, 2)
-        return arr.reshape(-1).view(np.longdouble)
-    return pack(ma, ea, sa), pack(mb, eb, sb)
-
-
-def _deep_cancel_pairs(gap, n=120_000, seed=41):
-    """Opposite-sign normal pairs near 1 whose difference cancels 7 to 31
-    leading bits of the top significand word (x87.hpp add_fast's normalise
-    by ffbh of the top word and its funnel shift, every lz in 0..31):
-    gap 0: b's top 32-bit significand word = a's +- k; gap 1: a's top word
-    0x80000000 against b's 0xFFFFFFFF - k (2a - b is then about k * 2^32);
-    k = 2^j + a random part below 2^j for j in 0..24 (k in 1..2^25), the low
-    words random."""
-    r = O.splitmix64(seed + gap, 5 * n).reshape(5, n)
-    j = (r[0] % np.uint64(25)).astype(np.uint64)
-    k = (np.uint64(1) << j) + (r[1] & ((np.uint64(1) << j) - np.uint64(1)))
-    top = np.uint64(1 << 31)
-    if gap == 0:
-        ta = top + (r[2] >> np.uint64(33)) % (np.uint64(1 << 31) - np.uint64(1 << 26)) \
-            + np.uint64(1 << 25)
-        up = (r[3] & np.uint64(1)).astype(bool)
-        tb = np.where(up, ta + k, ta - k)
-        tb = np.minimum(tb, np.uint64(0xFFFFFFFF))
-    else:
-        ta = np.full(n, top, np.uint64)
-        tb = np.uint64(0xFFFFFFFF) - k + np.uint64(1)
-    ma = (ta << np.uint64(32)) | (r[3] >> np.uint64(32))
-    mb = (tb << np.uint64(32)) | (r[4] & np.uint64(0xFFFFFFFF))
-    ea = np.full(n, 16383, np.uint64) + (r[2] & np.uint64(3)) - np.uint64(1)
-    eb = ea - np.uint64(gap)
-    sa = (r[4] >> np.uint64(40)) & np.uint64(1)
-    sb = sa ^ np.uint64(1)
-
-    def pack(m, e, sg):
-        arr = np.zeros((n, 16), np.uint8)
-        arr[:, :8] = m.astype(np.uint64).view(np.uint8).reshape(n, 8)
-        arr[:, 8:10] = (e | (sg << np.uint64(15))).astype(np.uint16).view(np.uint8).reshape(n, 2)
-        return arr.reshape(-1).view(np.longdouble)
-    return pack(ma, ea, sa), pack(mb, eb, sb)
-
-
 @pytest.mark.parametrize("gap", [0, 1])
 def test_deep_cancellation_top_word(x87, gap):
     """add_fast's normalisation for every leading-zero count of the top
@@ -188,15 +102,7 @@ def test_equal_and_opposite_operands(x87):
     """a + a (carry out of the significand at every exponent, up to overflow)
     and a + (-a) (exact cancellation to +0), normal, denormal and special
     encodings alike."""
-    a = np.concatenate([raw_random(20_000, 31, m) for m in ("normal", "near", "low", "high",
-                                                             "any")])
-    raw = O.value_bytes(a).reshape(-1, 10).copy()
-    raw[::2, :7] = 0            # every other significand a power of two (2^63):
-    raw[::2, 7] = 0x80          # a + a carries out of the 64 bits exactly
-    a = O.from_value_bytes("longdouble", raw.reshape(-1))
-    neg = O.value_bytes(a).reshape(-1, 10).copy()
-    neg[:, 9] ^= 0x80
-    b = O.from_value_bytes("longdouble", neg.reshape(-1))
+    a, b = equal_opposite_operands()
     check(x87, a, a, use_ref=O.ref_lib() is not None)
     check(x87, a, b, use_ref=O.ref_lib() is not None)
 
@@ -243,23 +149,7 @@ def test_tie_of_exponent_and_top_word(x87):
     (the magnitude order's tie, x87.hpp add_fast's flag and add_near's
     negative-sum case): low words random, equal or one apart, both signs
     pairings, both operand orders."""
-    n = 100_000
-    r = O.splitmix64(61, 4 * n).reshape(4, n)
-    hi = (r[0] | np.uint64(1 << 63)) & np.uint64(0xFFFFFFFF00000000)
-    lo_a = r[1] & np.uint64(0xFFFFFFFF)
-    kind = r[2] % np.uint64(3)
-    lo_b = np.where(kind == 0, r[3] & np.uint64(0xFFFFFFFF),
-                    np.where(kind == 1, lo_a, (lo_a + np.uint64(1)) & np.uint64(0xFFFFFFFF)))
-    e = np.full(n, 16383, np.uint64) + (r[2] >> np.uint64(8)) % np.uint64(40) - np.uint64(20)
-    sa = (r[3] >> np.uint64(40)) & np.uint64(1)
-    sb = np.where((r[3] >> np.uint64(41)) & np.uint64(3) == 0, sa, sa ^ np.uint64(1))
-
-    def pack(m, sg):
-        arr = np.zeros((n, 16), np.uint8)
-        arr[:, :8] = m.astype(np.uint64).view(np.uint8).reshape(n, 8)
-        arr[:, 8:10] = (e | (sg << np.uint64(15))).astype(np.uint16).view(np.uint8).reshape(n, 2)
-        return arr.reshape(-1).view(np.longdouble)
-    a, b = pack(hi | lo_a, sa), pack(hi | lo_b, sb)
+    a, b = tie_pairs(100_000)
     check(x87, a, b, use_ref=O.ref_lib() is not None)
     check(x87, b, a, use_ref=O.ref_lib() is not None)
 
@@ -411,19 +301,7 @@ def test_team_fold_minmax(x87, op, P):
     with NaNs, pseudo-denormals and unsupported encodings in some elements
     (the compare-by-compare fold)."""
     n = 60_000
-    pool = np.zeros((12, 10), np.uint8)
-
-    def enc(m, e, sgn):
-        b = np.zeros(10, np.uint8)
-        b[:8] = np.frombuffer(np.uint64(m).tobytes(), np.uint8)
-        b[8:10] = np.frombuffer(np.uint16(e | (sgn << 15)).tobytes(), np.uint8)
-        return b
-    vals = [(0, 0, 0), (0, 0, 1), (1 << 40, 0, 0), (1 << 40, 0, 1), (1 << 63, 0x7FFF, 0),
-            (1 << 63, 0x7FFF, 1), (0xC000000000000000, 0x3FFF, 0), (0xC000000000000000, 0x3FFF, 1),
-            (1 << 63, 1, 0), (1 << 63, 1, 1), (0x8000000000000001, 0x7FFE, 0),
-            (0x8000000000000001, 0x7FFE, 1)]
-    for i, v in enumerate(vals):
-        pool[i] = enc(*v)
+    pool = TIE_POOL
     specials = O.value_bytes(raw_random(n, 900, "any")).reshape(-1, 10)
     srcs = []
     for p in range(P):
