@@ -119,6 +119,18 @@ hipError_t launch_team_loc(int type, int op, int P, int ndst, void *const *val_d
                            int *const *loc_dsts, const void *const *val_srcs,
                            const int *const *loc_srcs, const int *member_locs, size_t n,
                            hipStream_t s);
+// Float-accumulated sum of half / bfloat16 sources (team.hip): for i < n and
+// every q < ndst, dsts[q][i] = out(widen(srcs[0][i]) + ... + widen(srcs[P-1][i])),
+// ONE float add per source, ascending, by elem_ops.hpp WsumStep; out narrows
+// once to `type` (out_type == type) or keeps the float (out_type == T_FLOAT).
+// 1 <= P <= 8; ndst is 1, or P with P >= 2.  carry (device floats, or null):
+// its element starts the accumulator and srcs[0] takes an add like the rest
+// -- a later chunk of a fold over more than 8 members; with a float target
+// and ndst = 1, dsts[0] may be the carry itself (every element is read and
+// written by one lane).  Otherwise targets must not overlap sources.
+// Multi-launch above max_launch_threads().
+hipError_t launch_team_wsum(int type, int out_type, int P, int ndst, void *const *dsts,
+                            const void *const *srcs, const float *carry, size_t n, hipStream_t s);
 // n elements of the identity of (type, op) (scan_host.hpp scan_identity) at
 // dst, any alignment; long double's padding bytes zero (team.hip)
 hipError_t launch_scan_fill(int type, int op, void *dst, size_t n, hipStream_t s);
@@ -163,6 +175,12 @@ bool host_fold(int type, int op, void *acc, const void *in, size_t n);
 bool host_fold_loc_supported(int type, int op);
 bool host_fold_loc(int type, int op, void *val, int *loc, const void *in_val, const int *in_loc,
                    int in_const, size_t n);
+// The same for osgpu_reduce_wsum (elem_ops.hpp WsumStep over wsum_host.hpp's
+// loops; type half or bfloat16): acc[k] = widen(src[k]); acc[k] += widen(in[k])
+// by one float add; out[k] = narrow(acc[k])
+bool host_wsum_widen(int type, float *acc, const void *src, size_t n);
+bool host_wsum_add(int type, float *acc, const void *in, size_t n);
+bool host_wsum_narrow(int type, void *out, const float *acc, size_t n);
 // One range between HBM and pinned host memory mapped into the GPU (either
 // side may be the host's device view): a fixed grid (OSGPU_HOST_COPY_GRID,
 // default 256 workgroups) sized for one PCIe link, not for HBM (copy.hip)

@@ -362,6 +362,51 @@ template <typename T, int OP> struct LocStep {
     }
 };
 
+// ------------------------------------------------ float-accumulated sum
+// The steps of osgpu_reduce_wsum (include/osgpu_reduce.h Part 1i) for
+// H = half_t / bf16_t: the members' values are added in a FLOAT accumulator
+// and narrowed once.
+//   widen   exact, NaNs included: a 16-bit NaN keeps sign, payload and its
+//           signalling bit (in integers: v_cvt_f32_f16 would quiet it);
+//   add     one float add by the SSE rule above (add<float>): a NaN
+//           accumulator stays, quieted, else a NaN operand is taken, quieted,
+//           else inf - inf gives 0xFFC00000;
+//   narrow  RNE (narrow() above); a NaN accumulator is TRUNCATED -- bfloat16
+//           bits >> 16, half sign | 0x7C00 | mantissa >> 13 -- which is
+//           lossless: every NaN the accumulator can hold is a widened 16-bit
+//           NaN, quieted or not, or the default NaN.
+// widen_fast / the plain + are the streaming kernels' branch-free forms: equal
+// to the exact ones whenever the FINAL accumulator is no NaN (a NaN, once met
+// or made, stays through every later add).
+OSGPU_EHD float widen_nan(half_t x)
+{
+    return flt(((uint32_t) (x.u & 0x8000u) << 16) | 0x7f800000u | ((uint32_t) (x.u & 0x3ffu) << 13));
+}
+OSGPU_EHD float widen_nan(bf16_t x) { return flt((uint32_t) x.u << 16); }
+OSGPU_EHD half_t truncate_nan(uint32_t u, half_t)
+{
+    return half_t{(uint16_t) (((u >> 16) & 0x8000u) | 0x7c00u | ((u >> 13) & 0x3ffu))};
+}
+OSGPU_EHD bf16_t truncate_nan(uint32_t u, bf16_t) { return bf16_t{(uint16_t) (u >> 16)}; }
+
+template <typename H> struct WsumStep {
+    OSGPU_EHD static float widen(H x)
+    {
+        if (__builtin_expect(isnan_(x), 0)) return widen_nan(x);
+        return osgpu::widen(x);
+    }
+    OSGPU_EHD static float widen_fast(H x) { return osgpu::widen(x); }
+    OSGPU_EHD static float add(float acc, H x) { return osgpu::add<float>(acc, widen(x)); }
+    OSGPU_EHD static H narrow(float acc)
+    {
+        if (__builtin_expect(isnan_(acc), 0)) return truncate_nan(bits(acc), H{});
+        return osgpu::narrow(acc, H{});
+    }
+    // the target's element: the accumulator itself, or narrowed
+    OSGPU_EHD static void out(float acc, float &o) { o = acc; }
+    OSGPU_EHD static void out(float acc, H &o) { o = narrow(acc); }
+};
+
 // ------------------------------------------------------- branch-free folds
 // Fast<T, OP>::f is Elem<T, OP>::f without its NaN handling (the SSE rule,
 // the complex product's libgcc recovery): one instruction stream with no

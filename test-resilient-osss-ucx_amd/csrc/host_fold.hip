@@ -25,6 +25,7 @@
 
 #include "kernel_common.hpp"
 #include "loc_host.hpp"
+#include "wsum_host.hpp"
 #include "x87.hpp"
 
 #pragma clang fp contract(off)
@@ -105,6 +106,35 @@ bool host_fold_loc(int type, int op, void *val, int *loc, const void *in_val, co
     const LocFoldFn f = loc_fold_fn(type, op);
     if (!f) return false;
     f(val, loc, in_val, in_loc, in_const, n);
+    return true;
+}
+
+// osgpu_reduce_wsum's steps (elem_ops.hpp WsumStep) over wsum_host.hpp's loops
+bool host_wsum_widen(int type, float *acc, const void *src, size_t n)
+{
+    if (type == T_HALF)
+        rt::wsum_widen_n<WsumStep<half_t>>(acc, static_cast<const half_t *>(src), n);
+    else if (type == T_BFLOAT16)
+        rt::wsum_widen_n<WsumStep<bf16_t>>(acc, static_cast<const bf16_t *>(src), n);
+    else return false;
+    return true;
+}
+
+bool host_wsum_add(int type, float *acc, const void *in, size_t n)
+{
+    if (type == T_HALF) rt::wsum_add_n<WsumStep<half_t>>(acc, static_cast<const half_t *>(in), n);
+    else if (type == T_BFLOAT16)
+        rt::wsum_add_n<WsumStep<bf16_t>>(acc, static_cast<const bf16_t *>(in), n);
+    else return false;
+    return true;
+}
+
+bool host_wsum_narrow(int type, void *out, const float *acc, size_t n)
+{
+    if (type == T_HALF) rt::wsum_narrow_n<WsumStep<half_t>>(static_cast<half_t *>(out), acc, n);
+    else if (type == T_BFLOAT16)
+        rt::wsum_narrow_n<WsumStep<bf16_t>>(static_cast<bf16_t *>(out), acc, n);
+    else return false;
     return true;
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/osgpu_reduce.h"
 #include "combine.hpp"
 #include "loc_host.hpp"
+#include "wsum_host.hpp"
 #include "psync_board.hpp"
 #include "runtime.hpp"
 
@@ -1662,6 +1663,26 @@ int osgpu_team_loc(int type, int op, int P, int ndst, void *const *val_dsts, int
                                           member_locs, nelems, st);
     if (e != hipSuccess) {
         set_err("osgpu_team_loc: %s", hipGetErrorString(e));
+        return OSGPU_EHIP;
+    }
+    return OSGPU_OK;
+}
+
+int osgpu_team_wsum(int type, int out_type, int P, int ndst, void *const *dsts,
+                    const void *const *srcs, const float *carry, size_t nelems, void *hip_stream)
+{
+    bool ok = osgpu::rt::wsum_pair(type, out_type) && P >= 1 && P <= osgpu::kMaxTeam &&
+              (ndst == 1 || (ndst == P && P >= 2)) && dsts && srcs;
+    for (int p = 0; ok && p < P; p++) ok = srcs[p] != nullptr;
+    for (int q = 0; ok && q < ndst; q++) ok = dsts[q] != nullptr;
+    if (!ok) {
+        set_err("osgpu_team_wsum: bad arguments");
+        return OSGPU_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t) hip_stream : thread_stream("osgpu_team_wsum");
+    hipError_t e = osgpu::launch_team_wsum(type, out_type, P, ndst, dsts, srcs, carry, nelems, st);
+    if (e != hipSuccess) {
+        set_err("osgpu_team_wsum: %s", hipGetErrorString(e));
         return OSGPU_EHIP;
     }
     return OSGPU_OK;

@@ -26,7 +26,7 @@
 // The per-call scaffolding shared with shmem_collect.cpp is call_common.hpp.
 //
 // The other front doors (reduce-scatter, batched, scan, uniform, max/min with
-// location) have no forms of their own above the kernels: they share the
+// location, float-accumulated 16-bit sum) have no forms of their own above the kernels: they share the
 // reduce-to-all's prologue (begin_call, arrays_kind), its host route
 // (host_route_fold), its GETMEM chunk loop (getmem_chunks), its pull schedule
 // (symmetric_ptrs, fold_sources, run_pull) and its caller-first host fold
@@ -53,6 +53,7 @@
 #include "rscatter_host.hpp"
 #include "runtime.hpp"
 #include "scan_host.hpp"
+#include "wsum_host.hpp"
 
 namespace {
 
@@ -1596,6 +1597,201 @@ void reduce_loc(const char *name, int type, int op, void *target, int *loc_targe
     if (path_mode() == OSGPU_PATH_PULL || !run_loc_team(c)) run_loc_pull(c);
 }
 
+// ------------------------------------------- float-accumulated 16-bit sum
+//
+// osgpu_reduce_wsum: the uniform reduce's one ascending fold of half /
+// bfloat16 sources in a FLOAT accumulator, rounded once at the end -- or not at
+// all, into a float target (elem_ops.hpp WsumStep).  Paths: device heaps the
+// owner-computes kernel (launch_team_wsum with every member's targets) or the
+// pull form (the caller's target alone, 8 sources a launch, the float
+// accumulator carried between launches); host heaps the host fold and GETMEM.
+// No FUSED, STAGED, RCCL or push form.  The byte arithmetic and the chunk
+// walks are wsum_host.hpp's.
+
+static_assert((int) SCAN_T_FLOAT == (int) OSGPU_T_FLOAT, "wsum_host.hpp takes scan_host.hpp's codes");
+
+struct WsumCall : Call {  // nbytes: one source array
+    int out_type = 0;
+    size_t osz = 0;     // bytes of a target element: 2 or 4
+    size_t tbytes = 0;  // one target array
+    size_t abytes = 0;  // one float accumulator array
+};
+
+// TEAM: source and target symmetric, not overlapping, 2..8 members.  Every
+// member folds its shard of all targets.  Shards are cut by the 2-byte source
+// element, so a boundary is a multiple of 8 elements: 16 bytes of the source
+// stream and 32 of a float target's.
+bool run_wsum_team(const WsumCall &c)
+{
+    const int P = c.PE_size;
+    if (P < 2 || P > osgpu::kMaxTeam) return false;
+    if (ranges_overlap(c.target, c.tbytes, c.source, c.nbytes)) return false;
+    std::vector<char *> vs, vd;
+    if (!symmetric_ptrs(c, c.source, c.nbytes, vs) || !symmetric_ptrs(c, c.target, c.tbytes, vd))
+        return false;
+    std::vector<const void *> srcs(vs.begin(), vs.end());
+    std::vector<void *> dsts(vd.begin(), vd.end());
+    run_team_shards(
+        c, srcs, dsts, c.index_of(c.me), "team float-accumulated sum",
+        // run_team_shards moved the targets on by the source's element size:
+        // they are taken from the shard's element offset instead
+        [&](int np, void *const *, const void *const *sr, size_t n, hipStream_t st) {
+            const size_t lo = (size_t) ((const char *) sr[0] - (const char *) srcs[0]) / kWsumSrcBytes;
+            std::vector<void *> d(np);
+            for (int j = 0; j < np; j++) d[j] = vd[j] + lo * c.osz;
+            return osgpu::launch_team_wsum(c.type, c.out_type, np, np, d.data(), sr, nullptr, n, st);
+        },
+        kWsumSrcBytes);
+    return true;
+}
+
+// PULL: the caller folds all P sources itself, ascending, into its own target:
+// launches of at most 8 sources, the float accumulator carried from one to the
+// next -- in the target itself when that is float, else in scratch -- and only
+// the last launch narrows.  A target that overlaps the source is folded into
+// scratch and copied back after the exit barrier.
+void run_wsum_pull(const WsumCall &c)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size;
+    std::vector<char *> vs;
+    if (!symmetric_ptrs(c, c.source, c.nbytes, vs)) no_device_heap(c, "source", c.nbytes);
+    t_last_path = OSGPU_RAN_PULL;
+    DBG("%s PE %d: pull over %d members, ascending, float accumulator", c.name, c.me, P);
+    entry_sync(c.name, st);
+    barrier(c);  // every source is ready
+    const bool ov = ranges_overlap(c.target, c.tbytes, c.source, c.nbytes);
+    const bool cs = wsum_needs_carry_scratch(P, c.osz);
+    const size_t oslot = ov ? (c.tbytes + 15) & ~(size_t) 15 : 0;
+    char *scr = ov || cs ? (char *) device_scratch(c.name, c.me, oslot + (cs ? c.abytes : 0)) : nullptr;
+    void *out = ov ? (void *) scr : c.target;
+    float *acc = cs ? (float *) (scr + oslot) : (float *) out;  // a float target carries itself
+    wsum_for_source_chunks(P, [&](int first, int count, bool carry_in, bool last) {
+        const void *v[kWsumMaxSources];
+        for (int k = 0; k < count; k++) v[k] = vs[first + k];
+        void *dst = last ? out : (void *) acc;
+        launched(c.name, "float-accumulated sum launch",
+                 osgpu::launch_team_wsum(c.type, last ? c.out_type : (int) OSGPU_T_FLOAT, count, 1,
+                                         &dst, v, carry_in ? acc : nullptr, (size_t) c.nreduce, st));
+    });
+    stream_wait(c.name, st);
+    barrier(c);  // peers are done reading my source
+    if (ov) {
+        HIPCHK(c.name, hipMemcpyAsync(c.target, out, c.tbytes, hipMemcpyDeviceToDevice, st));
+        stream_wait(c.name, st);
+    }
+}
+
+// Host heaps, small calls: the fold on this PE's thread, ascending, one getmem
+// of the whole source per peer, in a float accumulator -- a float target that
+// does not overlap the source, else a temporary narrowed or copied after the
+// exit barrier.
+void run_wsum_host_fold(const WsumCall &c)
+{
+    t_last_path = OSGPU_RAN_HOST_FOLD;
+    const int P = c.PE_size;
+    const size_t N = (size_t) c.nreduce;
+    const bool direct = c.osz == kWsumAccBytes &&
+                        !ranges_overlap(c.target, c.tbytes, c.source, c.nbytes);
+    thread_local std::vector<float> tmp;
+    thread_local std::vector<unsigned char> peer;
+    if (!direct) tmp.resize(N);
+    peer.resize(c.nbytes);
+    float *acc = direct ? (float *) c.target : tmp.data();
+    barrier(c);  // every source is ready
+    bool ok = osgpu::host_wsum_widen(c.type, acc, host_input(c, c.source, 0, 0, c.nbytes, peer.data()), N);
+    for (int j = 1; ok && j < P; j++)
+        ok = osgpu::host_wsum_add(c.type, acc, host_input(c, c.source, j, 0, c.nbytes, peer.data()), N);
+    barrier(c);  // every peer is done reading my source
+    if (ok && !direct) {
+        if (c.osz == kWsumAccBytes) memcpy(c.target, acc, c.tbytes);
+        else ok = osgpu::host_wsum_narrow(c.type, c.target, acc, N);
+    }
+    if (!ok) fatal(c.name, "host fold: type %d", c.type);
+}
+
+// Host heaps above that: chunks of host_chunk_bytes() (wsum_chunk_elems), the
+// sources of a chunk pulled into pinned staging 8 at a time and folded on the
+// GPU, the float accumulator carried in device scratch.
+void run_wsum_host(const WsumCall &c)
+{
+    hipStream_t st = pe_stream(c.name, c.me);
+    const int P = c.PE_size, K = std::min(P, (int) kWsumMaxSources);
+    const size_t N = (size_t) c.nreduce;
+    t_last_path = OSGPU_RAN_GETMEM;
+    const bool ov = ranges_overlap(c.target, c.tbytes, c.source, c.nbytes);
+    HostTmp res(c, c.target, ov, c.tbytes);
+    barrier(c);  // every source is ready
+    // slots 0 .. K-1 the sources; then the accumulator and the result (device),
+    // the result (host)
+    const size_t chunk = wsum_chunk_elems(host_chunk_bytes(), N);
+    const size_t sb = chunk * kWsumSrcBytes, ab = chunk * kWsumAccBytes, in = (size_t) K * sb;
+    char *dbuf = (char *) device_scratch(c.name, c.me, in + 2 * ab);
+    char *hbuf = (char *) host_stage(c.name, c.me, in + ab);
+    float *dacc = (float *) (dbuf + in);
+    void *dout = dbuf + in + ab;
+    scan_for_chunks(N, chunk, [&](size_t off, size_t n) {
+        const size_t nsb = n * kWsumSrcBytes, nob = n * c.osz;
+        wsum_for_source_chunks(P, [&](int first, int count, bool carry_in, bool last) {
+            const void *v[kWsumMaxSources];
+            for (int k = 0; k < count; k++) {
+                char *hv = hbuf + (size_t) k * sb, *dv = dbuf + (size_t) k * sb;
+                const void *got = host_input(c, c.source, first + k, off * kWsumSrcBytes, nsb, hv);
+                if (got != hv) memcpy(hv, got, nsb);
+                HIPCHK(c.name, hipMemcpyAsync(dv, hv, nsb, hipMemcpyHostToDevice, st));
+                v[k] = dv;
+            }
+            void *dst = last ? dout : (void *) dacc;
+            launched(c.name, "float-accumulated sum launch",
+                     osgpu::launch_team_wsum(c.type, last ? c.out_type : (int) OSGPU_T_FLOAT, count,
+                                             1, &dst, v, carry_in ? dacc : nullptr, n, st));
+            stream_wait(c.name, st);  // the staging slots are reused by the next launch
+        });
+        char *hout = hbuf + in;
+        HIPCHK(c.name, hipMemcpyAsync(hout, dout, nob, hipMemcpyDeviceToHost, st));
+        stream_wait(c.name, st);
+        memcpy(res.out + off * c.osz, hout, nob);
+    });
+    barrier(c);  // every peer is done reading my source
+    res.finish(c.tbytes);
+}
+
+void reduce_wsum(const char *name, int type, int out_type, void *target, const void *source,
+                 int nreduce, int PE_start, int logPE_stride, int PE_size, long *pSync)
+{
+    if (!wsum_pair(type, out_type))
+        fatal(name, "type %d with out_type %d is no float-accumulated sum of this library "
+                    "(osgpu_has_reduce_wsum)", type, out_type);
+    WsumCall c;
+    c.out_type = out_type;
+    c.osz = wsum_out_size(type, out_type);
+    if (!begin_call(c, name, type, OSGPU_OP_SUM, target, source, nreduce, PE_start, logPE_stride,
+                    PE_size, pSync, nreduce <= 0))
+        return;
+    WsumBytes b;
+    if (!wsum_bytes(c.osz, nreduce, PE_size, &b))
+        fatal(name, "%d arrays of %d elements do not fit the address space", PE_size, nreduce);
+    c.nbytes = b.sbytes;
+    c.tbytes = b.tbytes;
+    c.abytes = b.abytes;
+    if (!target || !source) fatal(name, "a null array");
+
+    const Array arrays[] = {{target, b.tbytes}, {source, b.sbytes}};
+    int dev = -1;
+    if (arrays_kind(c, arrays, 2, &dev) == MEM_HOST) {
+        if (host_route_fold(c, host_path(), b.pulled_bound, true, "the float-accumulated sum"))
+            run_wsum_host_fold(c);
+        else
+            run_wsum_host(c);
+        return;
+    }
+    const DeviceGuard on_device(name, dev);
+    // the team kernel under every setting but OSGPU_PATH_PULL (RCCL never
+    // serves this call); an overlap, a target outside the heaps, one member
+    // and more than 8 take the pull form
+    if (path_mode() == OSGPU_PATH_PULL || !run_wsum_team(c)) run_wsum_pull(c);
+}
+
 }  // namespace
 
 extern "C" int osgpu_last_path(void) { return t_last_path; }
@@ -1794,4 +1990,22 @@ extern "C" void osgpu_reduce_loc(int type, int op, void *target, int *loc_target
 extern "C" int osgpu_has_reduce_loc(int type, int op)
 {
     return osgpu::rt::loc_pair(type, op) ? 1 : 0;
+}
+
+// ======================================================================
+// Part 1i: float-accumulated half / bfloat16 sum (no reference counterpart)
+// ======================================================================
+
+extern "C" void osgpu_reduce_wsum(int type, int out_type, void *target, const void *source,
+                                  int nreduce, int PE_start, int logPE_stride, int PE_size,
+                                  void *pWrk, long *pSync)
+{
+    (void) pWrk;  // as for the reduce-to-all: peers are read directly
+    reduce_wsum("osgpu_reduce_wsum", type, out_type, target, source, nreduce, PE_start,
+                logPE_stride, PE_size, pSync);
+}
+
+extern "C" int osgpu_has_reduce_wsum(int type, int out_type)
+{
+    return osgpu::rt::wsum_pair(type, out_type) ? 1 : 0;
 }

@@ -21,6 +21,7 @@
 #include "kernel_common.hpp"
 #include "loc_host.hpp"
 #include "scan_host.hpp"
+#include "wsum_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1170,6 +1171,202 @@ hipError_t launch_team_loc(int type, int op, int P, int ndst, void *const *val_d
             return hipErrorInvalidValue;
         }
     });
+}
+
+// ------------------------------------------- float-accumulated 16-bit sum
+// osgpu_reduce_wsum: the uniform reduce's ONE ascending fold of half_t /
+// bf16_t sources in a FLOAT accumulator, narrowed once (elem_ops.hpp
+// WsumStep), stored to ndst targets of the source's type or of float.  The
+// shape of team_loc_vec_kernel: a register form, no LDS and no barrier, one
+// GROUP of 8 elements per lane -- one 16-byte vector of every 16-bit stream,
+// two of every float stream (the carry, float targets) -- and ONE bounds test
+// around the body, so no load is conditional.  A lane issues its P (+ 2)
+// loads before the first use, widens (v_cvt_f32_f16 / a shift), folds with
+// P - 1 (+ 1) float adds per element, narrows once and stores ndst * (1 or 2)
+// vectors.
+// The NaN rule stays off the streaming path: a NaN, once met or made, stays
+// through every later add, so the accumulator is a NaN at the end exactly when
+// some step met one; each element's final accumulator is tested once and only
+// such an element is refolded by the exact steps.
+// CARRY: the accumulator starts at a float array's element (an earlier
+// chunk's result) and srcs[0] takes an add like every other member.  With a
+// float target and ndst = 1 the target may be the carry itself: a lane reads
+// its group before it stores it.
+constexpr int kWsumBlock = 256;  // groups per tile: one per lane
+
+template <typename T, typename OUT, int P>
+struct WsumPtrs {
+    const T *src[P];
+    OUT *dst[P];
+    const float *carry;
+};
+
+// one element by the exact steps
+template <typename T, typename OUT, int P, bool CARRY>
+__device__ __forceinline__ OUT wsum_elem(const T (&x)[P], int np, float c)
+{
+    using S = WsumStep<T>;
+    float acc = CARRY ? S::add(c, x[0]) : S::widen(x[0]);
+#pragma unroll
+    for (int p = 1; p < P; p++)
+        if (p < np) acc = S::add(acc, x[p]);
+    OUT r;
+    S::out(acc, r);
+    return r;
+}
+
+template <typename T, typename OUT, int P, bool CARRY>
+__global__ __launch_bounds__(kWsumBlock) void team_wsum_vec_kernel(WsumPtrs<T, OUT, P> a, int ndst,
+                                                                   size_t ngroups, size_t head,
+                                                                   size_t tail_start, int nedge)
+{
+    constexpr int G = 8;                  // elements per group
+    constexpr int NO = G * sizeof(OUT) / 16;  // vectors per group of a target: 1 or 2
+    constexpr int WO = 16 / sizeof(OUT);
+    using S = WsumStep<T>;
+    if (blockIdx.x == 0 && (int) threadIdx.x < nedge) {
+        const size_t e = edge_index(head, tail_start);
+        T x[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) x[p] = a.src[p][e];
+        const OUT r = wsum_elem<T, OUT, P, CARRY>(x, P, CARRY ? a.carry[e] : 0.0f);
+#pragma unroll
+        for (int q = 0; q < P; q++)
+            if (q < ndst) a.dst[q][e] = r;
+    }
+    const size_t j = (size_t) blockIdx.x * kWsumBlock + threadIdx.x;
+    if (j >= ngroups) return;
+    Vec16<T> in[P];
+    Vec16<float> cv[2];
+#pragma unroll
+    for (int p = 0; p < P; p++)
+        in[p].v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.src[p] + head) + j);
+    if (CARRY) {
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+            cv[u].v = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4 *>(a.carry + head) + j * 2 + u);
+    }
+    Vec16<OUT> out[NO];
+#pragma unroll
+    for (int e = 0; e < G; e++) {
+        float acc = S::widen_fast(in[0].e[e]);
+        if (CARRY) acc = cv[e / 4].e[e % 4] + acc;
+#pragma unroll
+        for (int p = 1; p < P; p++) acc = acc + S::widen_fast(in[p].e[e]);
+        if (__builtin_expect(acc != acc, 0)) {
+            T x[P];
+#pragma unroll
+            for (int p = 0; p < P; p++) x[p] = in[p].e[e];
+            out[e / WO].e[e % WO] =
+                wsum_elem<T, OUT, P, CARRY>(x, P, CARRY ? cv[e / 4].e[e % 4] : 0.0f);
+        } else {
+            S::out(acc, out[e / WO].e[e % WO]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < P; q++) {
+        if (q >= ndst) break;
+#pragma unroll
+        for (int u = 0; u < NO; u++)
+            __builtin_nontemporal_store(out[u].v,
+                                        reinterpret_cast<u32x4 *>(a.dst[q] + head) + j * NO + u);
+    }
+}
+
+// element-granular form (no common head aligns every pointer): np sources of
+// a table sized for kMaxTeam, so one instantiation serves every P
+template <typename T, typename OUT, bool CARRY>
+__global__ __launch_bounds__(kTeamBlock) void team_wsum_scalar_kernel(WsumPtrs<T, OUT, kMaxTeam> a,
+                                                                      int np, int ndst, size_t n)
+{
+    const size_t stride = (size_t) gridDim.x * kTeamBlock;
+    for (size_t k = (size_t) blockIdx.x * kTeamBlock + threadIdx.x; k < n; k += stride) {
+        T x[kMaxTeam];
+#pragma unroll
+        for (int p = 0; p < kMaxTeam; p++) x[p] = p < np ? a.src[p][k] : T{0};
+        const OUT r = wsum_elem<T, OUT, kMaxTeam, CARRY>(x, np, CARRY ? a.carry[k] : 0.0f);
+#pragma unroll
+        for (int q = 0; q < kMaxTeam; q++)
+            if (q < ndst) a.dst[q][k] = r;
+    }
+}
+
+template <typename T, typename OUT, int P>
+static WsumPtrs<T, OUT, P> wsum_ptrs(int np, int ndst, void *const *dsts, const void *const *srcs,
+                                     const float *carry, size_t off)
+{
+    WsumPtrs<T, OUT, P> a;
+    for (int p = 0; p < P; p++) {
+        a.src[p] = p < np ? static_cast<const T *>(srcs[p]) + off : nullptr;
+        a.dst[p] = p < ndst ? static_cast<OUT *>(dsts[p]) + off : nullptr;
+    }
+    a.carry = carry ? carry + off : nullptr;
+    return a;
+}
+
+template <typename T, typename OUT, bool CARRY>
+static hipError_t wsum_launch(int P, int ndst, void *const *dsts, const void *const *srcs,
+                              const float *carry, size_t n, hipStream_t s)
+{
+    // the 16-bit pointers, and the float ones (loc_split's 4-byte stream)
+    const void *half[2 * kMaxTeam], *wide[kMaxTeam + 1];
+    int nh = 0, nw = 0;
+    for (int p = 0; p < P; p++) half[nh++] = srcs[p];
+    for (int q = 0; q < ndst; q++) {
+        if (sizeof(OUT) == 2) half[nh++] = dsts[q];
+        else wide[nw++] = dsts[q];
+    }
+    if (CARRY) wide[nw++] = carry;
+    const rt::LocSplit sp = rt::loc_split(sizeof(T), n, half, nh, wide, nw);
+    if (!sp.vec) {
+        size_t blocks = (n + kTeamBlock - 1) / kTeamBlock;
+        blocks = blocks > 8192 ? 8192 : blocks;
+        hipLaunchKernelGGL((team_wsum_scalar_kernel<T, OUT, CARRY>), dim3((unsigned) blocks),
+                           dim3(kTeamBlock), 0, s,
+                           wsum_ptrs<T, OUT, kMaxTeam>(P, ndst, dsts, srcs, carry, 0), P, ndst, n);
+        return hipGetLastError();
+    }
+    auto run = [&](auto pc) {
+        constexpr int PP = decltype(pc)::value;
+        // one tile of kWsumBlock groups per workgroup, in runs below the launch
+        // limit: the first launch takes the edges, the others shifted pointers
+        return for_each_tile_run(sp.ngroups, kWsumBlock, kWsumBlock, 1,
+                                 [&](size_t t0, size_t nt, size_t ng) {
+            const size_t off = t0 == 0 ? 0 : sp.head + t0 * kWsumBlock * rt::kWsumGroup;
+            hipLaunchKernelGGL((team_wsum_vec_kernel<T, OUT, PP, CARRY>), dim3((unsigned) nt),
+                               dim3(kWsumBlock), 0, s,
+                               wsum_ptrs<T, OUT, PP>(PP, ndst, dsts, srcs, carry, off), ndst, ng,
+                               t0 == 0 ? sp.head : (size_t) 0,
+                               t0 == 0 ? sp.tail_start : (size_t) 0, t0 == 0 ? sp.nedge : 0);
+            return hipGetLastError();
+        });
+    };
+    if (P == 1) return run(std::integral_constant<int, 1>{});
+    return dispatch_members(P, hipErrorInvalidValue, run);
+}
+
+template <typename T>
+static hipError_t wsum_launch_type(bool wide_out, int P, int ndst, void *const *dsts,
+                                   const void *const *srcs, const float *carry, size_t n,
+                                   hipStream_t s)
+{
+    if (wide_out)
+        return carry ? wsum_launch<T, float, true>(P, ndst, dsts, srcs, carry, n, s)
+                     : wsum_launch<T, float, false>(P, ndst, dsts, srcs, carry, n, s);
+    return carry ? wsum_launch<T, T, true>(P, ndst, dsts, srcs, carry, n, s)
+                 : wsum_launch<T, T, false>(P, ndst, dsts, srcs, carry, n, s);
+}
+
+hipError_t launch_team_wsum(int type, int out_type, int P, int ndst, void *const *dsts,
+                            const void *const *srcs, const float *carry, size_t n, hipStream_t s)
+{
+    if (!rt::wsum_pair(type, out_type) || !dsts || !srcs) return hipErrorInvalidValue;
+    if (P < 1 || P > kMaxTeam || !(ndst == 1 || (ndst == P && P >= 2))) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const bool wide_out = out_type == T_FLOAT;
+    if (type == T_HALF) return wsum_launch_type<half_t>(wide_out, P, ndst, dsts, srcs, carry, n, s);
+    return wsum_launch_type<bf16_t>(wide_out, P, ndst, dsts, srcs, carry, n, s);
 }
 
 }  // namespace osgpu

@@ -174,6 +174,10 @@ def load() -> ctypes.CDLL:
     L.osgpu_reduce_loc.restype = None
     L.osgpu_has_reduce_loc.argtypes = [i, i]
     L.osgpu_team_loc.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, sz, vp]
+    L.osgpu_reduce_wsum.argtypes = [i, i, vp, vp, i, i, i, i, vp, vp]
+    L.osgpu_reduce_wsum.restype = None
+    L.osgpu_has_reduce_wsum.argtypes = [i, i]
+    L.osgpu_team_wsum.argtypes = [i, i, i, i, vp, vp, vp, sz, vp]
     L.osgpu_copy.argtypes = [vp, vp, vp, i, vp]
     L.osgpu_copy_strided.argtypes = [i, vp, vp, vp, vp, vp, i, vp]
     L.osgpu_team_combine.argtypes = [i, i, i, vp, vp, sz, vp]
@@ -511,6 +515,30 @@ def team_loc(t: str, op: str, val_dsts, loc_dsts, val_srcs, loc_srcs, n: int, me
                           ml, n, stream)
     if rc != 0 and check:
         raise RuntimeError(f"osgpu_team_loc({t},{op}) = {rc}: {L.osgpu_last_error().decode()}")
+    return rc
+
+
+def reduce_wsum(t: str, out_t: str):
+    """osgpu_reduce_wsum bound to the codes of (t, out_t), t "half" or
+    "bfloat16", out_t the same or "float": a function of (target, source,
+    nreduce, PE_start, logPE_stride, PE_size, pWrk, pSync); every member
+    receives the sum accumulated in float, rounded once (or not at all)."""
+    f, tc, oc = load().osgpu_reduce_wsum, type_code(t), type_code(out_t)
+    return lambda *args: f(tc, oc, *args)
+
+
+def team_wsum(t: str, out_t: str, dsts, srcs, n: int, carry: int | None = None,
+              stream: int | None = None, check: bool = True) -> int:
+    """Enqueue the widening kernel: every dsts[q] = the float-accumulated sum
+    of srcs[0] .. srcs[P-1] (device ptrs), as out_t; len(dsts) is 1 or
+    len(srcs).  carry: a device array of n floats that starts the accumulator.
+    Returns the status; check=True raises on a non-zero one."""
+    L = load()
+    P, D = len(srcs), len(dsts)
+    rc = L.osgpu_team_wsum(type_code(t), type_code(out_t), P, D, (ctypes.c_void_p * D)(*dsts),
+                           (ctypes.c_void_p * P)(*srcs), carry, n, stream)
+    if rc != 0 and check:
+        raise RuntimeError(f"osgpu_team_wsum({t},{out_t}) = {rc}: {L.osgpu_last_error().decode()}")
     return rc
 
 
